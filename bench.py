@@ -6,6 +6,11 @@ via torch.distributed.run for N>1 (one rank per GPU over RCCL). W untimed
 warmup steps, then exactly K timed steps bracketed by barrier+synchronize;
 MAX elapsed over ranks; rank 0 prints ONE JSON line.
 
+A plain run does only that. `--dump-outputs DIR` additionally writes the
+last timed step's results as .npy files (same arguments => same inputs, so
+two builds can be compared output for output); `--full` is where secondary
+measurements belong (none exist yet).
+
 Synthetic data (random tokens), random-init weights (no network access).
 """
 import argparse
@@ -50,8 +55,63 @@ def parse_args():
     p.add_argument("--act-ckpt", action="store_true",
                    help="enable activation checkpointing (default off: "
                    "288 GB HBM3E fits full activations at these configs)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed "
+                        "step computed (its micro-step losses, a fixed "
+                        "seeded sample of the updated weights and their "
+                        "per-tensor norms) to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements; there are "
+                        "none at present (a plain run is already only "
+                        "setup, warmup, the timed steps and the result "
+                        "line), so this changes nothing yet")
     p.add_argument("--local_rank", type=int, default=-1)
     return p.parse_args()
+
+
+# elements sampled per parameter tensor by --dump-outputs: ~300 tensors of
+# an 8B model x 4096 x 4 B stays far below the 64 MB budget
+DUMP_SAMPLE = 4096
+
+
+def dump_outputs(out_dir, losses, model):
+    """Write the last timed step's results as .npy files.
+
+    loss.npy            float32 [grad_accum]: loss of each micro-step of
+                        that step
+    weights_sample.npy  float32: seeded sample of every parameter after
+                        that step (this rank's shard under ZeRO-3),
+                        concatenated in named_parameters() order
+    weights_norm.npy    float64 [n_tensors]: L2 norm of each of those
+                        tensors, a steadier figure than single elements,
+                        which an lr-sized bf16 update can flip
+    The sample indices depend only on the tensor sizes, so two builds run
+    with the same arguments write element-for-element comparable files.
+    """
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            torch.stack([l.detach().float().reshape(()) for l in losses])
+            .cpu().numpy().astype(np.float32))
+    gen = torch.Generator().manual_seed(20240607)
+    chunks, norms = [], []
+    for name, p in model.named_parameters():
+        t = getattr(p, "ds_tensor", None)
+        if t is None:
+            t = p.data
+        if t.numel() == 0 and getattr(p, "ds_numel", p.numel()) > 0:
+            raise RuntimeError(f"--dump-outputs: {name} has no resident "
+                               "data to sample (offloaded parameter)")
+        t = t.detach().reshape(-1)
+        norms.append(torch.linalg.vector_norm(t.double()).cpu())
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=gen)
+            t = t[idx.to(t.device)]
+        chunks.append(t.float().cpu())
+    np.save(os.path.join(out_dir, "weights_sample.npy"),
+            torch.cat(chunks).numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "weights_norm.npy"),
+            torch.stack(norms).numpy().astype(np.float64))
 
 
 def main():
@@ -153,8 +213,10 @@ def main():
     bufs = [torch.randint(0, cfg.vocab_size, (B, S_local), device=device)
             for _ in range(n_bufs)]
     step_idx = [0]
+    step_losses = []  # micro-step losses of the latest step (device scalars)
 
     def one_step():
+        step_losses.clear()
         for _ in range(args.grad_accum):
             data = bufs[step_idx[0] % n_bufs]
             step_idx[0] += 1
@@ -162,6 +224,7 @@ def main():
                 loss = engine(data, labels=data, seq_offset=seq_off)
             else:
                 loss = engine(data, labels=data)
+            step_losses.append(loss.detach())
             engine.backward(loss)
             engine.step()
         return loss
@@ -190,6 +253,9 @@ def main():
                          torch.cuda.is_available() else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, step_losses, model)
 
     global_batch = B * args.grad_accum * (world // sp_world)
     # with SP, ranks of one SP group share a sample (S_local tokens each)

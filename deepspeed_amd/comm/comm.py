@@ -281,3 +281,7 @@ def log_summary(show_straggler=False):
 def destroy_process_group():
     if is_initialized():
         torch_dist.destroy_process_group()
+    # the cached group handles are stale now, and each one keeps its
+    # backend (and the backend's worker threads) alive until it is dropped
+    from . import groups
+    groups.reset_groups()

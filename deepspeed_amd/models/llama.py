@@ -243,6 +243,13 @@ class LlamaModel(nn.Module):
         self.norm = LlamaRMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
         cos, sin = build_rope_cache(cfg.max_position_embeddings, cfg.head_dim,
                                     cfg.rope_theta)
+        # the table is computed on the host; under a `torch.device(...)`
+        # context it must follow the weights, or the HIP rope kernel would
+        # be handed host pointers. A meta build keeps the real host table:
+        # the buffers are not persistent, so nothing could restore them.
+        dev = self.embed_tokens.weight.device
+        if dev.type != "meta":
+            cos, sin = cos.to(dev), sin.to(dev)
         self.register_buffer("rope_cos", cos, persistent=False)
         self.register_buffer("rope_sin", sin, persistent=False)
 

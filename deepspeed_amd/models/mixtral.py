@@ -71,6 +71,10 @@ class MixtralForCausalLM(nn.Module):
         self.lm_head = nn.Linear(cfg.hidden_size, cfg.vocab_size, bias=False)
         cos, sin = build_rope_cache(cfg.max_position_embeddings, cfg.head_dim,
                                     cfg.rope_theta)
+        # host-computed table follows the weights (see LlamaModel)
+        dev = self.embed_tokens.weight.device
+        if dev.type != "meta":
+            cos, sin = cos.to(dev), sin.to(dev)
         self.register_buffer("rope_cos", cos, persistent=False)
         self.register_buffer("rope_sin", sin, persistent=False)
         self.apply(self._init_weights)

@@ -88,6 +88,17 @@ void rope(at::Tensor dst, at::Tensor src, at::Tensor cos, at::Tensor sin,
   TORCH_CHECK(src.scalar_type() == at::kBFloat16 && src.is_contiguous());
   TORCH_CHECK(src.dim() == 4, "rope expects [B,S,H,D]");
   int B = src.size(0), S = src.size(1), H = src.size(2), D = src.size(3);
+  // the kernel dereferences the table on the device: reject host tensors
+  // and tables shorter than the sequence instead of faulting
+  TORCH_CHECK(cos.device() == src.device() && sin.device() == src.device() &&
+                  dst.device() == src.device(),
+              "rope: cos/sin/dst must be on the same device as src");
+  TORCH_CHECK(cos.scalar_type() == at::kFloat && cos.is_contiguous() &&
+                  sin.scalar_type() == at::kFloat && sin.is_contiguous(),
+              "rope: cos/sin must be contiguous fp32");
+  TORCH_CHECK(cos.numel() >= (long long)S * (D / 2) &&
+                  sin.numel() >= (long long)S * (D / 2),
+              "rope: cos/sin table shorter than [S, D/2]");
   auto stream = c10::hip::getCurrentHIPStream();
   int block = 256;
   if ((D / 2) % 8 == 0) {

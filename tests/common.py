@@ -4,6 +4,7 @@ Modeled on the reference's DistributedTest mechanism
 (`tests/unit/common.py:139,427`): N local processes, file-store rendezvous,
 gloo on CPU / nccl(RCCL) on GPU.
 """
+import gc
 import os
 import pickle
 import tempfile
@@ -38,6 +39,17 @@ def _worker(rank, world_size, fn, args, kwargs, init_file, result_dir, backend):
     finally:
         if dist.is_initialized():
             dist.destroy_process_group()
+        # deepspeed_amd caches group handles in module globals. While one
+        # is alive its ProcessGroupGloo is not destroyed, so its worker
+        # threads are not joined; one that releases its last work item
+        # (a tensor, which needs the GIL) once the interpreter is already
+        # finalising is ended by pthread_exit inside a noexcept frame:
+        # "terminate called without an active exception", exit -6, after
+        # a passed test. Drop the handles and collect, so the backends are
+        # destroyed and their threads joined while the interpreter lives.
+        from deepspeed_amd.comm import groups
+        groups.reset_groups()
+        gc.collect()
 
 
 def run_distributed(fn, world_size=2, backend=None, args=(), kwargs=None,

@@ -104,7 +104,11 @@ def test_fp8_quant_kernels_match_torch():
         for e5m2, fmax, dt in ((False, E4M3_MAX, torch.float8_e4m3fn),
                                (True, E5M2_MAX, torch.float8_e5m2)):
             scale = (amax[0] / fmax).clamp(min=1e-12)
-            ref8, _ = _quant(x, dt, fmax)
+            # torch-op reference in fp32, as the kernels compute: on a bf16
+            # tensor _quant rounds 1/scale and the product to bf16 before
+            # the fp8 cast, and that double rounding alone moved ~2% of
+            # the codes by one ULP (2.02% measured for e4m3 at 192x4096)
+            ref8, _ = _quant(x.float(), dt, fmax)
             y = ext.fp8_cast(x, scale, e5m2).view(dt)
             # rounding mode at halfway points may differ by one ULP;
             # check the DEQUANTIZED error against the format's ULP bound
@@ -114,6 +118,7 @@ def test_fp8_quant_kernels_match_torch():
                 f"e5m2={e5m2}: recon err {recon_err} > {ulp_bound}"
             mismatch = (y.view(torch.int8) != ref8.view(torch.int8)) \
                 .float().mean().item()
+            print(f"M={M} K={K} e5m2={e5m2}: code mismatch {mismatch}")
             # e5m2 (2 mantissa bits) hits round-to-nearest-even halfway
             # cases more often; one-ULP disagreements are benign (the
             # dequantized-error bound above is the real check)

@@ -65,7 +65,24 @@ def test_ragged_decode_long_context_split():
 
 def test_serving_engine_uses_ragged_kernel():
     """Continuous-batching decode routes through the pool-direct kernel
-    and generates the same tokens as the masked-SDPA fallback."""
+    and generates the same tokens as the masked-SDPA fallback.
+
+    Both paths greedy-decode a random-init bf16 model, whose top logits
+    are frequently within a bf16 rounding step of each other, and one
+    flipped tie used to change every later token of that request. So the
+    fallback run is teacher-forced with the kernel run's tokens: every
+    decode step of the two runs sees the same context, the fallback's own
+    argmax is what gets compared, and wherever the two disagree the
+    kernel's token must be a near-tie in the fallback's logits.
+    Tie tolerance: logits are bf16 (8 significant bits), so at magnitude
+    |l| their spacing is at most 2^-7*|l|; allowing 2 steps of rounding
+    difference on each of the two logits compared gives 4 steps,
+    i.e. max|logit| / 32.
+    Since every step now sees the same context, the two paths' logits are
+    also compared directly: at every step they must agree within that
+    same 4-step allowance over the whole vocabulary (the paths differ only
+    in the order of fp32 accumulation and one bf16 rounding of the
+    attention output per layer)."""
     from deepspeed_amd.inference.serving import ContinuousBatchingEngine
     from deepspeed_amd.models.llama import LLAMA_CONFIGS, LlamaForCausalLM
     torch.manual_seed(0)
@@ -73,27 +90,67 @@ def test_serving_engine_uses_ragged_kernel():
     with torch.device("cuda"):
         model = LlamaForCausalLM(cfg).bfloat16().eval()
 
-    def run(force_fallback):
+    def run(force_fallback, forced=None):
         eng = ContinuousBatchingEngine(model, max_batch=4)
         if force_fallback:
             for c in eng.caches:
                 c._use_ragged = False
         else:
             assert all(c._use_ragged for c in eng.caches)
-        g = torch.Generator().manual_seed(3)
-        for i in range(3):
-            eng.add_request(torch.randint(0, cfg.vocab_size, (8 + 3 * i,),
-                                          generator=g),
-                            max_new_tokens=12)
-        out = eng.run()
-        return [out[k] for k in sorted(out)]
+        own = {}        # rid -> this path's own greedy tokens
+        margins = {}    # (rid, k) -> (max logit - logit of forced token, tol)
+        seen = {}       # (rid, k) -> fp32 logits this path sampled from
+        greedy = eng._sample
 
-    fast = run(False)
-    slow = run(True)
-    flat_f = [t for rr in fast for t in (rr.tolist()
-              if hasattr(rr, "tolist") else rr)]
-    flat_s = [t for rr in slow for t in (rr.tolist()
-              if hasattr(rr, "tolist") else rr)]
+        def sample(logits, req):
+            tok = greedy(logits, req)
+            k = len(req.generated)
+            own.setdefault(req.rid, []).append(tok)
+            lf = logits.float()
+            seen[(req.rid, k)] = lf.cpu()
+            if forced is None:
+                return tok
+            margins[(req.rid, k)] = (float(lf.max() - lf[forced[req.rid][k]]),
+                                     float(lf.abs().max()) / 32)
+            return forced[req.rid][k]
+
+        eng._sample = sample
+        g = torch.Generator().manual_seed(3)
+        prompts = {}
+        for i in range(3):
+            p = torch.randint(0, cfg.vocab_size, (8 + 3 * i,), generator=g)
+            prompts[eng.add_request(p, max_new_tokens=12)] = p.tolist()
+        out = eng.run()
+        for rid in sorted(out):   # the engine returns prompt + what it fed
+            fed = forced[rid] if forced is not None else own[rid]
+            assert out[rid].tolist() == prompts[rid] + fed
+        return [prompts[rid] + own[rid] for rid in sorted(out)], own, \
+            margins, seen
+
+    fast, fast_own, _, fast_logits = run(False)
+    slow, slow_own, margins, slow_logits = run(True, forced=fast_own)
+    flat_f = [t for rr in fast for t in rr]
+    flat_s = [t for rr in slow for t in rr]
+    assert len(flat_f) == len(flat_s) == 8 + 11 + 14 + 3 * 12
     same = sum(int(a == b) for a, b in zip(flat_f, flat_s))
     total = len(flat_f)
+    ties = {key: margins[key] for key in margins
+            if fast_own[key[0]][key[1]] != slow_own[key[0]][key[1]]}
+    print(f"token agreement {same}/{total}; disagreements "
+          f"(rid, step) -> (margin, tolerance): {ties}")
+    assert sorted(fast_logits) == sorted(slow_logits)
+    gaps = {key: (float((fast_logits[key] - slow_logits[key]).abs().max()),
+                  float(slow_logits[key].abs().max()) / 32)
+            for key in sorted(slow_logits)}
+    worst = max(gaps, key=lambda key: gaps[key][0] / gaps[key][1])
+    print(f"largest logit gap relative to its tolerance at (rid, step) "
+          f"{worst}: {gaps[worst]}")
     assert same / total > 0.9, f"token agreement {same}/{total}"
+    for key, (gap, tol) in gaps.items():
+        assert gap <= tol, \
+            f"request/step {key}: kernel and fallback logits differ by " \
+            f"{gap} > {tol}"
+    for key, (margin, tol) in ties.items():
+        assert margin <= tol, \
+            f"request/step {key}: kernel token is no near-tie for the " \
+            f"fallback (logit margin {margin} > {tol})"
