@@ -16,13 +16,14 @@ __global__ void adam_kernel_f32(float* __restrict__ p,
                                 short* __restrict__ out16,  // optional bf16 out
                                 long long n, float lr, float beta1, float beta2,
                                 float eps, float bc1, float bc2, int adamw,
-                                float wd, float gscale) {
+                                float wd, float gscale, int vec_ok) {
   const float step_size = lr / bc1;
   const float bc2_sqrt = sqrtf(bc2);
   long long i0 = (long long)(blockIdx.x) * blockDim.x + threadIdx.x;
   long long stride = (long long)gridDim.x * blockDim.x;
-  // vectorized main loop: 4 floats per lane
-  long long n4 = n / 4;
+  // vectorized main loop: 4 floats per lane; vec_ok: p/g/m/v 16-byte and
+  // out16 8-byte aligned (host-checked), else everything takes the tail loop
+  long long n4 = vec_ok ? n / 4 : 0;
   const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
   f32x4* p4 = reinterpret_cast<f32x4*>(p);
   f32x4* m4 = reinterpret_cast<f32x4*>(m);
@@ -75,6 +76,34 @@ __global__ void adam_kernel_f32(float* __restrict__ p,
   }
 }
 
+// Shared argument contract of the multi-tensor optimizers: fp32 contiguous
+// state lists of equal length and matching numel, optional bf16 out16.
+static void check_opt_lists(
+    const std::vector<at::Tensor>& params,
+    std::initializer_list<const std::vector<at::Tensor>*> states,
+    const std::vector<at::Tensor>& out16) {
+  for (auto* s : states)
+    TORCH_CHECK(s->size() == params.size(),
+                "optimizer tensor lists must have equal length");
+  TORCH_CHECK(out16.empty() || out16.size() == params.size(),
+              "out16 must be empty or one tensor per param");
+  for (size_t t = 0; t < params.size(); ++t) {
+    const at::Tensor& p = params[t];
+    TORCH_CHECK(p.scalar_type() == at::kFloat, "fp32 masters expected");
+    CHECK_ARG(p, at::kFloat);
+    for (auto* s : states) {
+      const at::Tensor& st = (*s)[t];
+      CHECK_ARG(st, at::kFloat);
+      CHECK_LIKE(st, p);
+    }
+    if (!out16.empty()) {
+      const at::Tensor& o = out16[t];
+      CHECK_ARG(o, at::kBFloat16);
+      CHECK_LIKE(o, p);
+    }
+  }
+}
+
 void multi_tensor_adam(std::vector<at::Tensor> params,
                        std::vector<at::Tensor> grads,
                        std::vector<at::Tensor> exp_avgs,
@@ -89,17 +118,19 @@ void multi_tensor_adam(std::vector<at::Tensor> params,
     bc1 = 1.f - powf((float)beta1, (float)step);
     bc2 = 1.f - powf((float)beta2, (float)step);
   }
+  check_opt_lists(params, {&grads, &exp_avgs, &exp_avg_sqs}, out16);
   auto stream = c10::hip::getCurrentHIPStream();
   for (size_t t = 0; t < params.size(); ++t) {
     auto& p = params[t];
-    TORCH_CHECK(p.scalar_type() == at::kFloat, "adam: fp32 masters expected");
     long long n = p.numel();
     short* o16 = nullptr;
-    if (!out16.empty()) {
-      TORCH_CHECK(out16[t].scalar_type() == at::kBFloat16);
-      TORCH_CHECK(out16[t].numel() == n);
+    if (!out16.empty())
       o16 = reinterpret_cast<short*>(out16[t].data_ptr());
-    }
+    int vec_ok = ptr_aligned(p.data_ptr(), 16) &&
+                 ptr_aligned(grads[t].data_ptr(), 16) &&
+                 ptr_aligned(exp_avgs[t].data_ptr(), 16) &&
+                 ptr_aligned(exp_avg_sqs[t].data_ptr(), 16) &&
+                 (o16 == nullptr || ptr_aligned(o16, 8));
     int block = 256;
     int grid = grid_for(n / 4 + 1, block);
     hipLaunchKernelGGL(adam_kernel_f32, dim3(grid), dim3(block), 0,
@@ -109,7 +140,7 @@ void multi_tensor_adam(std::vector<at::Tensor> params,
                        exp_avg_sqs[t].data_ptr<float>(), o16, n, (float)lr,
                        (float)beta1, (float)beta2, (float)eps, bc1, bc2,
                        (int)adamw_mode, (float)weight_decay,
-                       (float)grad_scale);
+                       (float)grad_scale, vec_ok);
     HIP_CHECK_KERNEL();
   }
 }
@@ -138,6 +169,7 @@ void multi_tensor_lion(std::vector<at::Tensor> params,
                        std::vector<at::Tensor> exp_avgs, double lr,
                        double beta1, double beta2, double weight_decay,
                        std::vector<at::Tensor> out16) {
+  check_opt_lists(params, {&grads, &exp_avgs}, out16);
   auto stream = c10::hip::getCurrentHIPStream();
   for (size_t t = 0; t < params.size(); ++t) {
     long long n = params[t].numel();
@@ -179,6 +211,7 @@ void multi_tensor_adagrad(std::vector<at::Tensor> params,
                           std::vector<at::Tensor> sq_accums, double lr,
                           double eps, double weight_decay,
                           std::vector<at::Tensor> out16) {
+  check_opt_lists(params, {&grads, &sq_accums}, out16);
   auto stream = c10::hip::getCurrentHIPStream();
   for (size_t t = 0; t < params.size(); ++t) {
     long long n = params[t].numel();
@@ -274,7 +307,10 @@ void multi_tensor_lamb(std::vector<at::Tensor> params,
     bc1 = 1.f - powf((float)beta1, (float)step);
     bc2 = 1.f - powf((float)beta2, (float)step);
   }
+  check_opt_lists(params, {&grads, &updates, &exp_avgs, &exp_avg_sqs}, out16);
+  CHECK_ARG(workspace, at::kFloat);
   TORCH_CHECK(workspace.numel() >= (long)(2 * params.size()));
+  if (!params.empty()) CHECK_ON(workspace, params[0]);
   auto stream = c10::hip::getCurrentHIPStream();
   float* ws = workspace.data_ptr<float>();
   for (size_t t = 0; t < params.size(); ++t) {

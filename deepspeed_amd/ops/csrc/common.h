@@ -7,6 +7,8 @@
 #include <hip/hip_fp16.h>
 #include <c10/hip/HIPStream.h>
 
+#include <cstdint>
+
 #define WAVE 64
 #define DEV_INLINE __device__ __forceinline__
 
@@ -19,6 +21,25 @@ static inline int grid_for(long long total_threads, int block) {
 }
 
 using bf16 = __hip_bfloat16;
+
+// Host-side argument contract. Every entry point reinterprets data_ptr(), so
+// a wrong dtype/layout/device must raise instead of reading garbage.
+#define CHECK_ARG(t, dt)                                                   \
+  TORCH_CHECK((t).defined() && (t).is_cuda() && (t).scalar_type() == (dt) && \
+                  (t).is_contiguous(),                                     \
+              #t " must be a contiguous " #dt " device tensor")
+#define CHECK_LIKE(t, ref)                                                 \
+  TORCH_CHECK((t).device() == (ref).device() && (t).numel() == (ref).numel(), \
+              #t " must match " #ref " in device and numel")
+#define CHECK_ON(t, ref)                                                   \
+  TORCH_CHECK((t).device() == (ref).device(),                              \
+              #t " must be on the same device as " #ref)
+
+// The vector paths (bf16x8 / f32x4 / uint2) need the address aligned to the
+// vector width; views into flat ZeRO buffers can start at any element.
+static inline bool ptr_aligned(const void* p, size_t bytes) {
+  return (reinterpret_cast<uintptr_t>(p) % bytes) == 0;
+}
 
 // 16-byte vector of 8 bf16 (guide G13: always vectorize bf16 loads).
 struct alignas(16) bf16x8 {

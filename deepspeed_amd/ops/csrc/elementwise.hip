@@ -8,7 +8,8 @@
 
 #include "common.h"
 
-// q/k layout: [B, S, H, D] bf16 contiguous; cos/sin: [S, D/2] fp32.
+// q/k layout: [B, S, H, D] bf16 contiguous; cos/sin: [>= pos0 + S, D/2] fp32;
+// sequence position s uses table row s + pos0.
 // Llama "rotate_half" pairing: (d, d + D/2).
 // vectorized: each lane rotates 8 consecutive pairs (bf16x8 loads from both
 // halves, float4x2 table loads) — scalar version measured 2.5 TB/s, this
@@ -31,8 +32,8 @@ __global__ void rope_kernel(short* __restrict__ dst,
     int s = (int)(rem2 % S);
     long long b = rem2 / S;
     long long base = ((b * S + s) * (long long)H + h) * D + d8 * 8;
-    const float* crow = cs + (long long)s * half + d8 * 8;
-    const float* srow = sn + (long long)s * half + d8 * 8;
+    const float* crow = cs + (long long)(s + pos0) * half + d8 * 8;
+    const float* srow = sn + (long long)(s + pos0) * half + d8 * 8;
     bf16x8 x1 = *reinterpret_cast<const bf16x8*>(src + base);
     bf16x8 x2 = *reinterpret_cast<const bf16x8*>(src + base + half);
     f32x4 c0 = *reinterpret_cast<const f32x4*>(crow);
@@ -73,8 +74,8 @@ __global__ void rope_kernel_scalar(short* __restrict__ dst,
     int s = (int)(rem2 % S);
     long long b = rem2 / S;
     long long base = ((b * S + s) * (long long)H + h) * D;
-    float c = cs[(long long)(s) * half + d];
-    float sv = sn[(long long)(s) * half + d];
+    float c = cs[(long long)(s + pos0) * half + d];
+    float sv = sn[(long long)(s + pos0) * half + d];
     if (backward) sv = -sv;
     float x1 = bf2f(src[base + d]);
     float x2 = bf2f(src[base + d + half]);
@@ -85,9 +86,13 @@ __global__ void rope_kernel_scalar(short* __restrict__ dst,
 
 void rope(at::Tensor dst, at::Tensor src, at::Tensor cos, at::Tensor sin,
           long pos0, bool backward) {
-  TORCH_CHECK(src.scalar_type() == at::kBFloat16 && src.is_contiguous());
+  CHECK_ARG(src, at::kBFloat16);
+  CHECK_ARG(dst, at::kBFloat16);
+  CHECK_LIKE(dst, src);
   TORCH_CHECK(src.dim() == 4, "rope expects [B,S,H,D]");
   int B = src.size(0), S = src.size(1), H = src.size(2), D = src.size(3);
+  TORCH_CHECK(D % 2 == 0, "rope: D must be even");
+  if (src.numel() == 0) return;
   // the kernel dereferences the table on the device: reject host tensors
   // and tables shorter than the sequence instead of faulting
   TORCH_CHECK(cos.device() == src.device() && sin.device() == src.device() &&
@@ -96,12 +101,17 @@ void rope(at::Tensor dst, at::Tensor src, at::Tensor cos, at::Tensor sin,
   TORCH_CHECK(cos.scalar_type() == at::kFloat && cos.is_contiguous() &&
                   sin.scalar_type() == at::kFloat && sin.is_contiguous(),
               "rope: cos/sin must be contiguous fp32");
-  TORCH_CHECK(cos.numel() >= (long long)S * (D / 2) &&
-                  sin.numel() >= (long long)S * (D / 2),
-              "rope: cos/sin table shorter than [S, D/2]");
+  TORCH_CHECK(pos0 >= 0, "rope: pos0 must be >= 0");
+  TORCH_CHECK((long long)(pos0 + S) * (D / 2) <= cos.numel() &&
+                  (long long)(pos0 + S) * (D / 2) <= sin.numel(),
+              "rope: cos/sin table shorter than [pos0 + S, D/2]");
   auto stream = c10::hip::getCurrentHIPStream();
   int block = 256;
-  if ((D / 2) % 8 == 0) {
+  bool vec = (D / 2) % 8 == 0 && ptr_aligned(src.data_ptr(), 16) &&
+             ptr_aligned(dst.data_ptr(), 16) &&
+             ptr_aligned(cos.data_ptr(), 16) &&
+             ptr_aligned(sin.data_ptr(), 16);
+  if (vec) {
     long long total_vec = (long long)B * S * H * (D / 16);
     int grid = grid_for(total_vec, block);
     hipLaunchKernelGGL(rope_kernel, dim3(grid), dim3(block), 0,
@@ -131,10 +141,11 @@ void rope_inplace(at::Tensor t, at::Tensor cos, at::Tensor sin, long pos0,
 // -------- SwiGLU: y = silu(g) * u; packed gu = [..., 2*I] (g|u) ----------
 __global__ void swiglu_fwd_kernel(const short* __restrict__ g,
                                   const short* __restrict__ u,
-                                  short* __restrict__ y, long long n) {
+                                  short* __restrict__ y, long long n,
+                                  int vec_ok) {
   long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long stride = (long long)gridDim.x * blockDim.x;
-  long long n8 = n / 8;
+  long long n8 = vec_ok ? n / 8 : 0;  // vec_ok: all bases 16-byte aligned
   for (long long i = i0; i < n8; i += stride) {
     bf16x8 gv = reinterpret_cast<const bf16x8*>(g)[i];
     bf16x8 uv = reinterpret_cast<const bf16x8*>(u)[i];
@@ -158,10 +169,11 @@ __global__ void swiglu_bwd_kernel(const short* __restrict__ dy,
                                   const short* __restrict__ g,
                                   const short* __restrict__ u,
                                   short* __restrict__ dg,
-                                  short* __restrict__ du, long long n) {
+                                  short* __restrict__ du, long long n,
+                                  int vec_ok) {
   long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long stride = (long long)gridDim.x * blockDim.x;
-  long long n8 = n / 8;
+  long long n8 = vec_ok ? n / 8 : 0;
   for (long long i = i0; i < n8; i += stride) {
     bf16x8 dv = reinterpret_cast<const bf16x8*>(dy)[i];
     bf16x8 gv = reinterpret_cast<const bf16x8*>(g)[i];
@@ -190,35 +202,51 @@ __global__ void swiglu_bwd_kernel(const short* __restrict__ dy,
 }
 
 at::Tensor swiglu_fwd(at::Tensor g, at::Tensor u) {
-  TORCH_CHECK(g.scalar_type() == at::kBFloat16 && g.is_contiguous());
+  CHECK_ARG(g, at::kBFloat16);
+  CHECK_ARG(u, at::kBFloat16);
+  CHECK_LIKE(u, g);
   auto y = at::empty_like(g);
   long long n = g.numel();
+  if (n == 0) return y;
+  int vec_ok = ptr_aligned(g.data_ptr(), 16) && ptr_aligned(u.data_ptr(), 16) &&
+               ptr_aligned(y.data_ptr(), 16);
   auto stream = c10::hip::getCurrentHIPStream();
   int block = 256;
-  int grid = grid_for(n / 8 + 1, block);
+  int grid = grid_for(vec_ok ? n / 8 + 1 : n, block);
   hipLaunchKernelGGL(swiglu_fwd_kernel, dim3(grid), dim3(block), 0,
                      stream.stream(),
                      reinterpret_cast<const short*>(g.data_ptr()),
                      reinterpret_cast<const short*>(u.data_ptr()),
-                     reinterpret_cast<short*>(y.data_ptr()), n);
+                     reinterpret_cast<short*>(y.data_ptr()), n, vec_ok);
   HIP_CHECK_KERNEL();
   return y;
 }
 
 std::vector<at::Tensor> swiglu_bwd(at::Tensor dy, at::Tensor g, at::Tensor u) {
+  CHECK_ARG(g, at::kBFloat16);
+  CHECK_ARG(u, at::kBFloat16);
+  CHECK_ARG(dy, at::kBFloat16);
+  CHECK_LIKE(u, g);
+  CHECK_LIKE(dy, g);
   auto dg = at::empty_like(g);
   auto du = at::empty_like(u);
   long long n = g.numel();
+  if (n == 0) return {dg, du};
+  int vec_ok = ptr_aligned(dy.data_ptr(), 16) &&
+               ptr_aligned(g.data_ptr(), 16) &&
+               ptr_aligned(u.data_ptr(), 16) &&
+               ptr_aligned(dg.data_ptr(), 16) &&
+               ptr_aligned(du.data_ptr(), 16);
   auto stream = c10::hip::getCurrentHIPStream();
   int block = 256;
-  int grid = grid_for(n / 8 + 1, block);
+  int grid = grid_for(vec_ok ? n / 8 + 1 : n, block);
   hipLaunchKernelGGL(swiglu_bwd_kernel, dim3(grid), dim3(block), 0,
                      stream.stream(),
                      reinterpret_cast<const short*>(dy.data_ptr()),
                      reinterpret_cast<const short*>(g.data_ptr()),
                      reinterpret_cast<const short*>(u.data_ptr()),
                      reinterpret_cast<short*>(dg.data_ptr()),
-                     reinterpret_cast<short*>(du.data_ptr()), n);
+                     reinterpret_cast<short*>(du.data_ptr()), n, vec_ok);
   HIP_CHECK_KERNEL();
   return {dg, du};
 }

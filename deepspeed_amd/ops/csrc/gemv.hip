@@ -12,7 +12,7 @@
 __global__ void gemv_bf16_kernel(const short* __restrict__ W,  // [N,K]
                                  const short* __restrict__ x,  // [B,K]
                                  short* __restrict__ y,        // [B,N]
-                                 int N, int K) {
+                                 int N, int K, int vec) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + wave;
@@ -21,7 +21,7 @@ __global__ void gemv_bf16_kernel(const short* __restrict__ W,  // [N,K]
   const short* wr = W + (long long)row * K;
   const short* xr = x + (long long)b * K;
   float acc = 0.f;
-  const int K8 = K / 8;
+  const int K8 = vec ? K / 8 : 0;  // vec: K % 8 == 0, 16 B-aligned W and x
   for (int i = lane; i < K8; i += 64) {
     bf16x8 wv = reinterpret_cast<const bf16x8*>(wr)[i];
     bf16x8 xv = reinterpret_cast<const bf16x8*>(xr)[i];
@@ -39,7 +39,7 @@ __global__ void gemv_bf16_kernel(const short* __restrict__ W,  // [N,K]
 __global__ void gemv_bf16_splitk_kernel(const short* __restrict__ W,
                                         const short* __restrict__ x,
                                         short* __restrict__ y, int N,
-                                        int K) {
+                                        int K, int vec) {
   __shared__ float lds[4];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -48,7 +48,7 @@ __global__ void gemv_bf16_splitk_kernel(const short* __restrict__ W,
   const short* wr = W + (long long)row * K;
   const short* xr = x + (long long)b * K;
   float acc = 0.f;
-  const int K8 = K / 8;
+  const int K8 = vec ? K / 8 : 0;  // vec: K % 8 == 0, 16 B-aligned W and x
   for (int i = threadIdx.x; i < K8; i += 256) {
     bf16x8 wv = reinterpret_cast<const bf16x8*>(wr)[i];
     bf16x8 xv = reinterpret_cast<const bf16x8*>(xr)[i];
@@ -66,11 +66,20 @@ __global__ void gemv_bf16_splitk_kernel(const short* __restrict__ W,
 }
 
 at::Tensor gemv_bf16(at::Tensor W, at::Tensor x) {
-  TORCH_CHECK(W.scalar_type() == at::kBFloat16 && W.is_contiguous());
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_contiguous());
+  CHECK_ARG(W, at::kBFloat16);
+  CHECK_ARG(x, at::kBFloat16);
+  CHECK_ON(x, W);
+  TORCH_CHECK(W.dim() == 2 && W.size(1) > 0 && x.dim() >= 1 &&
+                  x.size(-1) == W.size(1),
+              "gemv_bf16: W must be [N,K] and x [...,K]");
   int N = W.size(0), K = W.size(1);
   int B = x.numel() / K;
   auto y = at::empty({B, N}, x.options());
+  if (B == 0 || N == 0) return y;
+  int vec = (K % 8 == 0 && ptr_aligned(W.data_ptr(), 16) &&
+             ptr_aligned(x.data_ptr(), 16))
+                ? 1
+                : 0;
   auto stream = c10::hip::getCurrentHIPStream();
   if (N < 4096) {
     dim3 grid(N, B);
@@ -78,13 +87,13 @@ at::Tensor gemv_bf16(at::Tensor W, at::Tensor x) {
                        stream.stream(),
                        reinterpret_cast<const short*>(W.data_ptr()),
                        reinterpret_cast<const short*>(x.data_ptr()),
-                       reinterpret_cast<short*>(y.data_ptr()), N, K);
+                       reinterpret_cast<short*>(y.data_ptr()), N, K, vec);
   } else {
     dim3 grid((N + 3) / 4, B);
     hipLaunchKernelGGL(gemv_bf16_kernel, grid, dim3(256), 0, stream.stream(),
                        reinterpret_cast<const short*>(W.data_ptr()),
                        reinterpret_cast<const short*>(x.data_ptr()),
-                       reinterpret_cast<short*>(y.data_ptr()), N, K);
+                       reinterpret_cast<short*>(y.data_ptr()), N, K, vec);
   }
   HIP_CHECK_KERNEL();
   return y;

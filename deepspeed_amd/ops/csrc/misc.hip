@@ -10,10 +10,12 @@
 
 __global__ void accum_bf16_f32_kernel(float* __restrict__ dst,
                                       const short* __restrict__ src,
-                                      long long n, float scale) {
+                                      long long n, float scale,
+                                      int vec_ok) {
   long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long stride = (long long)gridDim.x * blockDim.x;
-  long long n4 = n / 4;
+  // vec_ok: dst 16-byte and src 8-byte aligned (host-checked), else scalar
+  long long n4 = vec_ok ? n / 4 : 0;
   for (long long i = i0; i < n4; i += stride) {
     uint2 sv = reinterpret_cast<const uint2*>(src)[i];
     const short* s = reinterpret_cast<const short*>(&sv);
@@ -27,28 +29,31 @@ __global__ void accum_bf16_f32_kernel(float* __restrict__ dst,
 }
 
 void accum_bf16_to_f32(at::Tensor dst, at::Tensor src, double scale) {
-  TORCH_CHECK(dst.scalar_type() == at::kFloat && dst.is_contiguous());
-  TORCH_CHECK(src.scalar_type() == at::kBFloat16 && src.is_contiguous());
-  TORCH_CHECK(dst.numel() == src.numel());
+  CHECK_ARG(dst, at::kFloat);
+  CHECK_ARG(src, at::kBFloat16);
+  CHECK_LIKE(src, dst);
   long long n = dst.numel();
+  if (n == 0) return;
+  int vec_ok = ptr_aligned(dst.data_ptr(), 16) && ptr_aligned(src.data_ptr(), 8);
   auto stream = c10::hip::getCurrentHIPStream();
   int block = 256;
   int grid = grid_for(n / 4 + 1, block);
   hipLaunchKernelGGL(accum_bf16_f32_kernel, dim3(grid), dim3(block), 0,
                      stream.stream(), dst.data_ptr<float>(),
                      reinterpret_cast<const short*>(src.data_ptr()), n,
-                     (float)scale);
+                     (float)scale, vec_ok);
   HIP_CHECK_KERNEL();
 }
 
 template <int BLOCK>
 __global__ void l2norm_sq_kernel(const float* __restrict__ x, long long n,
-                                 float* __restrict__ out /* accum */) {
+                                 float* __restrict__ out /* accum */,
+                                 int vec_ok) {
   __shared__ float lds[BLOCK / WAVE];
   long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long stride = (long long)gridDim.x * blockDim.x;
   float acc = 0.f;
-  long long n4 = n / 4;
+  long long n4 = vec_ok ? n / 4 : 0;
   for (long long i = i0; i < n4; i += stride) {
     f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
 #pragma unroll
@@ -61,16 +66,21 @@ __global__ void l2norm_sq_kernel(const float* __restrict__ x, long long n,
 
 at::Tensor l2norm_sq(std::vector<at::Tensor> tensors) {
   TORCH_CHECK(!tensors.empty());
+  for (auto& t : tensors) {
+    CHECK_ARG(t, at::kFloat);
+    CHECK_ON(t, tensors[0]);
+  }
   auto out = at::zeros({1}, tensors[0].options().dtype(at::kFloat));
   auto stream = c10::hip::getCurrentHIPStream();
   constexpr int BLOCK = 256;
   for (auto& t : tensors) {
-    TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous());
     long long n = t.numel();
+    if (n == 0) continue;
+    int vec_ok = ptr_aligned(t.data_ptr(), 16);
     int grid = grid_for(n / 4 + 1, BLOCK);
     hipLaunchKernelGGL(l2norm_sq_kernel<BLOCK>, dim3(grid), dim3(BLOCK), 0,
                        stream.stream(), t.data_ptr<float>(), n,
-                       out.data_ptr<float>());
+                       out.data_ptr<float>(), vec_ok);
     HIP_CHECK_KERNEL();
   }
   return out;

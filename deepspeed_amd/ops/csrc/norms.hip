@@ -9,18 +9,36 @@
 
 #include "common.h"
 
+// Row kernels may take the bf16x8 path only when every row start is 16-byte
+// aligned: row stride a multiple of 8 elements and aligned base pointers.
+static inline int row_vec_ok(int H, std::initializer_list<const void*> ptrs) {
+  if (H % 8 != 0) return 0;
+  for (const void* p : ptrs)
+    if (!ptr_aligned(p, 16)) return 0;
+  return 1;
+}
+
+static inline void check_norm_args(const at::Tensor& x, const at::Tensor& w) {
+  CHECK_ARG(x, at::kBFloat16);
+  CHECK_ARG(w, at::kBFloat16);
+  CHECK_ON(w, x);
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0 && w.numel() == x.size(-1),
+              "weight must have x.size(-1) elements");
+}
+
 // ---------------------------------------------------------------- RMSNorm
 template <int BLOCK>
 __global__ void rmsnorm_fwd_kernel(const short* __restrict__ x,
                                    const short* __restrict__ w,
                                    short* __restrict__ y,
                                    float* __restrict__ rstd_out, int H,
-                                   float eps) {
+                                   float eps, int vec) {
   __shared__ float lds[BLOCK / WAVE];
   const long long row = blockIdx.x;
   const short* xr = x + row * (long long)H;
   short* yr = y + row * (long long)H;
-  int H8 = H / 8;
+  // vec: H % 8 == 0 and 16-byte-aligned bases (host-checked), else scalar
+  int H8 = vec ? H / 8 : 0;
   float ss = 0.f;
   for (int i = threadIdx.x; i < H8; i += BLOCK) {
     bf16x8 v = reinterpret_cast<const bf16x8*>(xr)[i];
@@ -56,14 +74,16 @@ __global__ void rmsnorm_bwd_dx_kernel(const short* __restrict__ dy,
                                       const short* __restrict__ x,
                                       const short* __restrict__ w,
                                       const float* __restrict__ rstd,
-                                      short* __restrict__ dx, int H) {
+                                      short* __restrict__ dx, int H,
+                                      int vec) {
   __shared__ float lds[BLOCK / WAVE];
   const long long row = blockIdx.x;
   const short* dyr = dy + row * (long long)H;
   const short* xr = x + row * (long long)H;
   short* dxr = dx + row * (long long)H;
   float rs = rstd[row];
-  int H8 = H / 8;
+  // vec: H % 8 == 0 and 16-byte-aligned bases (host-checked), else scalar
+  int H8 = vec ? H / 8 : 0;
   float dot = 0.f;
   for (int i = threadIdx.x; i < H8; i += BLOCK) {
     bf16x8 dv = reinterpret_cast<const bf16x8*>(dyr)[i];
@@ -113,38 +133,49 @@ __global__ void rmsnorm_bwd_dw_kernel(const short* __restrict__ dy,
 }
 
 std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor w, double eps) {
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_contiguous());
+  check_norm_args(x, w);
   int H = x.size(-1);
   long long rows = x.numel() / H;
   auto y = at::empty_like(x);
   auto rstd = at::empty({rows}, x.options().dtype(at::kFloat));
+  if (rows == 0) return {y, rstd};
   auto stream = c10::hip::getCurrentHIPStream();
   constexpr int BLOCK = 256;
+  int vec = row_vec_ok(H, {x.data_ptr(), w.data_ptr(), y.data_ptr()});
   hipLaunchKernelGGL(rmsnorm_fwd_kernel<BLOCK>, dim3(rows), dim3(BLOCK), 0,
                      stream.stream(),
                      reinterpret_cast<const short*>(x.data_ptr()),
                      reinterpret_cast<const short*>(w.data_ptr()),
                      reinterpret_cast<short*>(y.data_ptr()),
-                     rstd.data_ptr<float>(), H, (float)eps);
+                     rstd.data_ptr<float>(), H, (float)eps, vec);
   HIP_CHECK_KERNEL();
   return {y, rstd};
 }
 
 std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
                                     at::Tensor rstd) {
+  check_norm_args(x, w);
+  CHECK_ARG(dy, at::kBFloat16);
+  CHECK_LIKE(dy, x);
+  CHECK_ARG(rstd, at::kFloat);
+  CHECK_ON(rstd, x);
   int H = x.size(-1);
   long long rows = x.numel() / H;
+  TORCH_CHECK(rstd.numel() == rows, "rstd must have one entry per row");
   auto dx = at::empty_like(x);
   auto dw = at::zeros({H}, x.options().dtype(at::kFloat));
+  if (rows == 0) return {dx, dw};
   auto stream = c10::hip::getCurrentHIPStream();
   constexpr int BLOCK = 256;
+  int vec = row_vec_ok(
+      H, {dy.data_ptr(), x.data_ptr(), w.data_ptr(), dx.data_ptr()});
   hipLaunchKernelGGL(rmsnorm_bwd_dx_kernel<BLOCK>, dim3(rows), dim3(BLOCK), 0,
                      stream.stream(),
                      reinterpret_cast<const short*>(dy.data_ptr()),
                      reinterpret_cast<const short*>(x.data_ptr()),
                      reinterpret_cast<const short*>(w.data_ptr()),
                      rstd.data_ptr<float>(),
-                     reinterpret_cast<short*>(dx.data_ptr()), H);
+                     reinterpret_cast<short*>(dx.data_ptr()), H, vec);
   HIP_CHECK_KERNEL();
   int gy = rows > 4096 ? 64 : (rows > 512 ? 16 : 1);
   hipLaunchKernelGGL(rmsnorm_bwd_dw_kernel, dim3((H + 255) / 256, gy),
@@ -169,16 +200,19 @@ __global__ void layernorm_fwd_kernel(const short* __restrict__ x,
   const long long row = blockIdx.x;
   const short* xr = x + row * (long long)H;
   short* yr = y + row * (long long)H;
-  float s = 0.f, ss = 0.f;
-  for (int i = threadIdx.x; i < H; i += BLOCK) {
-    float f = bf2f(xr[i]);
-    s += f;
-    ss += f * f;
-  }
+  float s = 0.f;
+  for (int i = threadIdx.x; i < H; i += BLOCK) s += bf2f(xr[i]);
   s = block_reduce_sum<BLOCK>(s, lds);
-  ss = block_reduce_sum<BLOCK>(ss, lds);
   float mean = s / H;
-  float var = ss / H - mean * mean;
+  // two-pass variance: E[x^2] - mean^2 loses |mean|^2/var of the fp32
+  // mantissa (rows with a large offset); the row is L2-hot on re-read
+  float ss = 0.f;
+  for (int i = threadIdx.x; i < H; i += BLOCK) {
+    float d = bf2f(xr[i]) - mean;
+    ss += d * d;
+  }
+  ss = block_reduce_sum<BLOCK>(ss, lds);
+  float var = ss / H;
   float rstd = rsqrtf(var + eps);
   if (threadIdx.x == 0) {
     if (mean_out) mean_out[row] = mean;
@@ -246,11 +280,17 @@ __global__ void layernorm_bwd_dwdb_kernel(const short* __restrict__ dy,
 std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w,
                                       c10::optional<at::Tensor> b,
                                       double eps) {
+  check_norm_args(x, w);
+  if (b.has_value()) {
+    CHECK_ARG(*b, at::kBFloat16);
+    CHECK_LIKE(*b, w);
+  }
   int H = x.size(-1);
   long long rows = x.numel() / H;
   auto y = at::empty_like(x);
   auto mean = at::empty({rows}, x.options().dtype(at::kFloat));
   auto rstd = at::empty({rows}, x.options().dtype(at::kFloat));
+  if (rows == 0) return {y, mean, rstd};
   auto stream = c10::hip::getCurrentHIPStream();
   constexpr int BLOCK = 256;
   hipLaunchKernelGGL(
@@ -267,11 +307,21 @@ std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w,
 std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x,
                                       at::Tensor w, at::Tensor mean,
                                       at::Tensor rstd) {
+  check_norm_args(x, w);
+  CHECK_ARG(dy, at::kBFloat16);
+  CHECK_LIKE(dy, x);
+  CHECK_ARG(mean, at::kFloat);
+  CHECK_ARG(rstd, at::kFloat);
+  CHECK_ON(mean, x);
+  CHECK_ON(rstd, x);
   int H = x.size(-1);
   long long rows = x.numel() / H;
+  TORCH_CHECK(mean.numel() == rows && rstd.numel() == rows,
+              "mean/rstd must have one entry per row");
   auto dx = at::empty_like(x);
   auto dw = at::zeros({H}, x.options().dtype(at::kFloat));
   auto db = at::zeros({H}, x.options().dtype(at::kFloat));
+  if (rows == 0) return {dx, dw, db};
   auto stream = c10::hip::getCurrentHIPStream();
   constexpr int BLOCK = 256;
   hipLaunchKernelGGL(layernorm_bwd_dx_kernel<BLOCK>, dim3(rows), dim3(BLOCK),

@@ -85,9 +85,10 @@ __global__ void dequantize_fp8_kernel(const unsigned char* __restrict__ q,
 }
 
 std::vector<at::Tensor> quantize_int8(at::Tensor x, long group_size) {
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_contiguous());
+  CHECK_ARG(x, at::kBFloat16);
   long long total = x.numel();
-  TORCH_CHECK(total % group_size == 0, "numel % group_size != 0");
+  TORCH_CHECK(group_size > 0 && total > 0 && total % group_size == 0,
+              "numel % group_size != 0");
   long long groups = total / group_size;
   auto q = at::empty({total}, x.options().dtype(at::kChar));
   auto scales = at::empty({groups}, x.options().dtype(at::kFloat));
@@ -102,8 +103,21 @@ std::vector<at::Tensor> quantize_int8(at::Tensor x, long group_size) {
   return {q, scales};
 }
 
+// q [total] codes + fp32 scales, one per group of `group` elements
+static void check_dequant_args(const at::Tensor& q, at::ScalarType qdt,
+                               const at::Tensor& scales, long long total,
+                               long group) {
+  CHECK_ARG(q, qdt);
+  CHECK_ARG(scales, at::kFloat);
+  CHECK_ON(scales, q);
+  TORCH_CHECK(group > 0 && total > 0 &&
+                  scales.numel() >= (total + group - 1) / group,
+              "scales must hold one entry per group");
+}
+
 at::Tensor dequantize_int8(at::Tensor q, at::Tensor scales, long group_size) {
   long long total = q.numel();
+  check_dequant_args(q, at::kChar, scales, total, group_size);
   auto x = at::empty({total}, q.options().dtype(at::kBFloat16));
   auto stream = c10::hip::getCurrentHIPStream();
   int grid = grid_for(total, 256);
@@ -117,9 +131,10 @@ at::Tensor dequantize_int8(at::Tensor q, at::Tensor scales, long group_size) {
 }
 
 std::vector<at::Tensor> quantize_fp8(at::Tensor x, long group_size) {
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_contiguous());
+  CHECK_ARG(x, at::kBFloat16);
   long long total = x.numel();
-  TORCH_CHECK(total % group_size == 0);
+  TORCH_CHECK(group_size > 0 && total > 0 && total % group_size == 0,
+              "numel % group_size != 0");
   long long groups = total / group_size;
   auto q = at::empty({total}, x.options().dtype(at::kByte));
   auto scales = at::empty({groups}, x.options().dtype(at::kFloat));
@@ -136,6 +151,7 @@ std::vector<at::Tensor> quantize_fp8(at::Tensor x, long group_size) {
 
 at::Tensor dequantize_fp8(at::Tensor q, at::Tensor scales, long group_size) {
   long long total = q.numel();
+  check_dequant_args(q, at::kByte, scales, total, group_size);
   auto x = at::empty({total}, q.options().dtype(at::kBFloat16));
   auto stream = c10::hip::getCurrentHIPStream();
   int grid = grid_for(total, 256);
@@ -265,9 +281,10 @@ static void _launch_fp_em(int qbits, const at::Tensor& x, at::Tensor& q,
 }
 
 std::vector<at::Tensor> quantize_fp_em(at::Tensor x, long qbits, long group) {
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_contiguous());
+  CHECK_ARG(x, at::kBFloat16);
   TORCH_CHECK(qbits == 4 || qbits == 6 || qbits == 12);
   long long n = x.numel();
+  TORCH_CHECK(group > 0 && n > 0, "quantize_fp_em: empty input or group");
   long long ngroups = (n + group - 1) / group;
   auto q = at::empty({n}, x.options().dtype(at::kUInt16));
   auto scales = at::empty({ngroups}, x.options().dtype(at::kFloat));
@@ -281,6 +298,11 @@ std::vector<at::Tensor> quantize_fp_em(at::Tensor x, long qbits, long group) {
 at::Tensor dequantize_fp_em(at::Tensor q, at::Tensor scales, long qbits,
                             long group, std::vector<long> shape) {
   long long n = q.numel();
+  TORCH_CHECK(qbits == 4 || qbits == 6 || qbits == 12);
+  check_dequant_args(q, at::kUInt16, scales, n, group);
+  long long shape_numel = 1;
+  for (long d : shape) shape_numel *= d;
+  TORCH_CHECK(shape_numel == n, "shape does not match the code count");
   auto x = at::empty({n}, q.options().dtype(at::kBFloat16));
   auto stream = c10::hip::getCurrentHIPStream();
   int block = 256;
@@ -358,9 +380,10 @@ __global__ void dequantize_int4_kernel(const unsigned char* __restrict__ q,
 }
 
 std::vector<at::Tensor> quantize_int4(at::Tensor x, long group) {
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_contiguous());
-  TORCH_CHECK(group % 2 == 0);
+  CHECK_ARG(x, at::kBFloat16);
+  TORCH_CHECK(group > 0 && group % 2 == 0);
   long long n = x.numel();
+  TORCH_CHECK(n > 0, "quantize_int4: empty input");
   long long ngroups = (n + group - 1) / group;
   auto q = at::empty({ngroups * (group / 2)}, x.options().dtype(at::kByte));
   auto scales = at::empty({ngroups}, x.options().dtype(at::kFloat));
@@ -376,6 +399,9 @@ std::vector<at::Tensor> quantize_int4(at::Tensor x, long group) {
 
 at::Tensor dequantize_int4(at::Tensor q, at::Tensor scales, long group,
                            long numel) {
+  TORCH_CHECK(group > 0 && group % 2 == 0);
+  check_dequant_args(q, at::kByte, scales, numel, group);
+  TORCH_CHECK(q.numel() >= (numel + 1) / 2, "q shorter than numel / 2");
   auto x = at::empty({numel}, q.options().dtype(at::kBFloat16));
   auto stream = c10::hip::getCurrentHIPStream();
   long long pairs = (numel + 1) / 2;

@@ -9,10 +9,10 @@
 __global__ void bias_add_kernel(const short* __restrict__ a,
                                 const short* __restrict__ bias,
                                 short* __restrict__ y, long long total,
-                                int C) {
+                                int C, int vec_ok) {
   long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long stride = (long long)gridDim.x * blockDim.x;
-  long long t8 = total / 8;
+  long long t8 = vec_ok ? total / 8 : 0;  // vec_ok: a and y 16-byte aligned
   for (long long i = i0; i < t8; i += stride) {
     bf16x8 av = reinterpret_cast<const bf16x8*>(a)[i];
     long long base = i * 8;
@@ -40,11 +40,20 @@ __global__ void bias_add_add_kernel(const short* __restrict__ a,
 
 at::Tensor spatial_bias_add(at::Tensor a, at::Tensor bias,
                             c10::optional<at::Tensor> other) {
-  TORCH_CHECK(a.scalar_type() == at::kBFloat16 && a.is_contiguous());
+  CHECK_ARG(a, at::kBFloat16);
+  CHECK_ARG(bias, at::kBFloat16);
+  CHECK_ON(bias, a);
   int C = bias.numel();
-  TORCH_CHECK(a.size(-1) == C, "bias must match the last dim");
+  TORCH_CHECK(a.dim() >= 1 && C > 0 && a.size(-1) == C,
+              "bias must match the last dim");
+  if (other.has_value()) {
+    CHECK_ARG(*other, at::kBFloat16);
+    CHECK_LIKE(*other, a);
+  }
   long long total = a.numel();
   auto y = at::empty_like(a);
+  if (total == 0) return y;
+  int vec_ok = ptr_aligned(a.data_ptr(), 16) && ptr_aligned(y.data_ptr(), 16);
   auto stream = c10::hip::getCurrentHIPStream();
   int grid = grid_for(total / 8 + 1, 256);
   if (other.has_value()) {
@@ -59,7 +68,8 @@ at::Tensor spatial_bias_add(at::Tensor a, at::Tensor bias,
                        stream.stream(),
                        reinterpret_cast<const short*>(a.data_ptr()),
                        reinterpret_cast<const short*>(bias.data_ptr()),
-                       reinterpret_cast<short*>(y.data_ptr()), total, C);
+                       reinterpret_cast<short*>(y.data_ptr()), total, C,
+                       vec_ok);
   }
   HIP_CHECK_KERNEL();
   return y;

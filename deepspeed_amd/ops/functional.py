@@ -12,9 +12,13 @@ from .loader import get_ext
 class _RMSNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, eps):
+        # the kernels index rows as base + row*H: save the contiguous
+        # tensors, so backward reads the same memory forward did
+        x = x.contiguous()
+        weight = weight.contiguous()
         if x.is_cuda and x.dtype == torch.bfloat16:
             ext = get_ext(required=True)
-            y, rstd = ext.rmsnorm_fwd(x.contiguous(), weight.contiguous(), eps)
+            y, rstd = ext.rmsnorm_fwd(x, weight, eps)
         else:
             x32 = x.float()
             rstd = torch.rsqrt(x32.pow(2).mean(-1, keepdim=True) + eps)
@@ -50,10 +54,11 @@ def rms_norm(x, weight, eps=1e-5):
 class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps):
+        x = x.contiguous()
+        weight = weight.contiguous()
         if x.is_cuda and x.dtype == torch.bfloat16:
             ext = get_ext(required=True)
-            y, mean, rstd = ext.layernorm_fwd(x.contiguous(),
-                                              weight.contiguous(),
+            y, mean, rstd = ext.layernorm_fwd(x, weight,
                                               bias.contiguous()
                                               if bias is not None else None,
                                               eps)
@@ -111,8 +116,9 @@ class _RoPEFn(torch.autograd.Function):
         ctx.save_for_backward(cos, sin)
         if t.is_cuda and t.dtype == torch.bfloat16 and cos.dim() == 2:
             ext = get_ext(required=True)
+            t = t.contiguous()
             out = torch.empty_like(t)
-            ext.rope(out, t.contiguous(), cos, sin, 0, False)
+            ext.rope(out, t, cos, sin, 0, False)
         else:  # eager path also serves per-row positions (cos [B,S,half])
             out = _rope_torch(t, cos, sin, sign=1.0)
         return out
@@ -122,8 +128,9 @@ class _RoPEFn(torch.autograd.Function):
         cos, sin = ctx.saved_tensors
         if dy.is_cuda and dy.dtype == torch.bfloat16 and cos.dim() == 2:
             ext = get_ext(required=True)
+            dy = dy.contiguous()
             dx = torch.empty_like(dy)
-            ext.rope(dx, dy.contiguous(), cos, sin, 0, True)
+            ext.rope(dx, dy, cos, sin, 0, True)
         else:
             dx = _rope_torch(dy, cos, sin, sign=-1.0)
         return dx, None, None
@@ -165,10 +172,12 @@ def build_rope_cache(seq_len, head_dim, base=500000.0, device="cpu",
 class _SwiGLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, g, u):
+        g = g.contiguous()
+        u = u.contiguous()
         ctx.save_for_backward(g, u)
         if g.is_cuda and g.dtype == torch.bfloat16:
             ext = get_ext(required=True)
-            return ext.swiglu_fwd(g.contiguous(), u.contiguous())
+            return ext.swiglu_fwd(g, u)
         g32 = g.float()
         return (torch.nn.functional.silu(g32) * u.float()).to(g.dtype)
 
@@ -177,8 +186,7 @@ class _SwiGLUFn(torch.autograd.Function):
         g, u = ctx.saved_tensors
         if g.is_cuda and g.dtype == torch.bfloat16:
             ext = get_ext(required=True)
-            dg, du = ext.swiglu_bwd(dy.contiguous(), g.contiguous(),
-                                    u.contiguous())
+            dg, du = ext.swiglu_bwd(dy.contiguous(), g, u)
             return dg, du
         g32, u32, dy32 = g.float(), u.float(), dy.float()
         sig = torch.sigmoid(g32)
@@ -198,10 +206,11 @@ class _FusedCrossEntropyFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, targets, ignore_index):
+        logits = logits.contiguous()
+        targets = targets.contiguous()
         if logits.is_cuda and logits.dtype == torch.bfloat16:
             ext = get_ext(required=True)
-            loss, lse = ext.cross_entropy_fwd(logits.contiguous(), targets,
-                                              ignore_index)
+            loss, lse = ext.cross_entropy_fwd(logits, targets, ignore_index)
         else:
             l32 = logits.float()
             lse = torch.logsumexp(l32, dim=-1)

@@ -118,3 +118,13 @@ def test_tiny_llama_cpu_trains():
         opt.step()
         losses.append(loss.item())
     assert losses[-1] < losses[0]
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_strided_inputs_fwd_bwd_cpu(dtype):
+    """rms_norm / layer_norm / swiglu / fused_cross_entropy on transposed
+    and padded[:, :V] views, forward and backward, vs float64 of the view
+    (CPU fallback path; the GPU twin is in test_kernel_edges_gpu.py)."""
+    from edge_refs import strided_cases
+    fails = strided_cases(torch.device("cpu"), dtype)
+    assert not fails, "\n".join(fails)
