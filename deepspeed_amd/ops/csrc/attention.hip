@@ -2,37 +2,23 @@
 //
 // Role parity: reference uses CUTLASS/flash-attn kernels
 // (deepspeed/inference/v2/kernels, csrc/transformer/inference/csrc/softmax.cu).
-// MI355X-native design (guide §B "fused attention prefill"):
-//   - 4 waves/block, 64 q-rows per block (16 per wave), KV tiles of 64
-//   - mfma_f32_16x16x32_bf16; online softmax in fp32 registers
-//   - K tile staged in LDS with the ((row&7)<<4) XOR byte-swizzle
-//     (row-major [64][128] bf16 is otherwise a 16-way bank conflict)
-//   - V staged TRANSPOSED in LDS so the PV B-operand is a ds_read_b128
-//   - P staged per-wave in LDS (pad 8) to convert C-layout -> A-layout
-//   - causal masking; GQA via head-group indexing; saves per-row LSE for the
-//     backward pass
-// Correctness verified against fp32 torch reference (tests/test_ops_gpu.py,
-// asymmetric random inputs per guide G9).
+// MI355X-native design (guide §B "fused attention prefill"): one kernel,
+// flash_fwd_v5_kernel below — 8 waves/block, 256 q-rows per block (32 per
+// wave), KV tiles of 64, mfma_f32_32x32x16_bf16, online softmax in fp32
+// registers, causal and additive kv-column masking, GQA via head-group
+// indexing; saves per-row LSE for the backward pass.
+// A q row with no admissible kv column (fully masked) yields out = 0 and
+// lse = -inf.
+// Correctness: elementwise against a float64 reference with derived bounds
+// (tests/test_attention_edges_gpu.py, references in tests/attn_refs.py).
 #include <torch/extension.h>
 
 #include "common.h"
 
 using bf16x8_t = __attribute__((ext_vector_type(8))) short;
-using f32x4_t = __attribute__((ext_vector_type(4))) float;
 
-#define MFMA_BF16_16x16x32 __builtin_amdgcn_mfma_f32_16x16x32_bf16
-
-constexpr int QTILE = 128;  // q rows per block (8 waves x 16)
 constexpr int KVTILE = 64;  // kv rows per tile
-constexpr int DHEAD = 128;
-constexpr int KPAD = 0;            // K uses swizzle, no pad
-constexpr int VT_PAD = 8;          // Vt rows padded: [128][64+8]
-constexpr int P_PAD = 8;           // P rows padded: [16][64+8]
-
-// swizzle byte offset within a K row (16B granules spread across banks)
-DEV_INLINE int kswz(int row, int byte_off) {
-  return row * (DHEAD * 2) + (byte_off ^ ((row & 7) << 4));
-}
+constexpr int VT_PAD = 8;   // Vt rows padded: [DH][64+8]
 
 // Vt[d][kv] byte offset: pad-8 rows spread the d-read (2-way) and the
 // ((d>>5)&3)<<5 XOR spreads the 4 d-groups on the transpose write
@@ -41,221 +27,6 @@ DEV_INLINE int kswz(int row, int byte_off) {
 DEV_INLINE int vtswz(int d, int kv_byte) {
   return d * ((KVTILE + VT_PAD) * 2) + (kv_byte ^ (((d >> 5) & 3) << 5));
 }
-
-__launch_bounds__(512, 3)
-__global__ void flash_fwd_kernel(
-    const short* __restrict__ q,  // [B,S,Hq,D]
-    const short* __restrict__ k,  // [B,S,Hk,D]
-    const short* __restrict__ v,  // [B,S,Hk,D]
-    short* __restrict__ out,      // [B,S,Hq,D]
-    float* __restrict__ lse_out,  // [B,Hq,S]
-    int B, int S, int Hq, int Hk, float scale, int causal) {
-  __shared__ short k_lds[KVTILE * DHEAD];            // swizzled
-  __shared__ short vt_lds[DHEAD * (KVTILE + VT_PAD)];  // transposed
-  __shared__ short p_lds[8][16 * (KVTILE + P_PAD)];    // per-wave P
-
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int l15 = lane & 15;
-  const int l4 = lane >> 4;  // 0..3
-
-  const int qtile = blockIdx.x;
-  const int bh = blockIdx.y;
-  const int b = bh / Hq;
-  const int h = bh % Hq;
-  const int hk = h / (Hq / Hk);
-  const int qbase = qtile * QTILE;
-  const int wave_q = qbase + wave * 16;  // this wave's first q row
-
-  const long long q_row_stride = (long long)Hq * DHEAD;
-  const long long kv_row_stride = (long long)Hk * DHEAD;
-  const short* qp = q + ((long long)b * S) * q_row_stride + h * DHEAD;
-  const short* kp = k + ((long long)b * S) * kv_row_stride + hk * DHEAD;
-  const short* vp = v + ((long long)b * S) * kv_row_stride + hk * DHEAD;
-
-  // ---- load Q fragments: lane holds Q[wave_q + l15][l4*8 + j + 32*ks]
-  bf16x8_t qfrag[4];
-  {
-    int qrow = wave_q + l15;
-    const short* src = qp + (long long)qrow * q_row_stride;
-    bool valid = qrow < S;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      if (valid) {
-        qfrag[ks] = *reinterpret_cast<const bf16x8_t*>(src + ks * 32 + l4 * 8);
-      } else {
-        qfrag[ks] = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
-      }
-    }
-  }
-
-  // online softmax state: rows wave_q + l4*4 + r  (r = 0..3)
-  float m_run[4], l_run[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    m_run[r] = -INFINITY;
-    l_run[r] = 0.f;
-  }
-  f32x4_t o_acc[8];
-#pragma unroll
-  for (int dt = 0; dt < 8; ++dt) o_acc[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-  const int kv_end = causal ? min(S, qbase + QTILE) : S;
-  const int n_tiles = (kv_end + KVTILE - 1) / KVTILE;
-
-  for (int t = 0; t < n_tiles; ++t) {
-    const int kvbase = t * KVTILE;
-    // ---- stage K (async global_load_lds, pre-swizzled source) -----------
-    // wave w, pass p covers 1 KiB of linear K LDS: lane's dest is
-    // base + lane*16 (HW rule), so the SOURCE column carries the XOR
-    // (guide m173: swizzled layouts via pre-swizzled global address).
-    {
-      for (int pass = 0; pass < 2; ++pass) {
-        int linear = (pass * 8 + wave) * 1024 + lane * 16;
-        int row = linear >> 8;             // /256 bytes per row
-        int colbyte = linear & 255;
-        int src_col = colbyte ^ ((row & 7) << 4);
-        int grow = kvbase + row;
-        int srow = grow < S ? grow : S - 1;  // clamped; masked via -inf
-        const short* src = kp + (long long)srow * kv_row_stride +
-                           (src_col >> 1);
-        __builtin_amdgcn_global_load_lds(
-            reinterpret_cast<const unsigned int*>(src),
-            reinterpret_cast<unsigned int*>(
-                reinterpret_cast<char*>(k_lds) + (pass * 8 + wave) * 1024),
-            16, 0, 0);
-      }
-      // V transposed: coalesced row reads, XOR-spread scatter writes
-      int row = threadIdx.x >> 3;        // 0..63
-      int c0 = (threadIdx.x & 7) * 16;   // 0..112 step 16
-      int grow = kvbase + row;
-      const short* vrow = vp + (long long)grow * kv_row_stride;
-#pragma unroll
-      for (int cc = 0; cc < 2; ++cc) {
-        int col = c0 + cc * 8;
-        bf16x8_t vv8;
-        if (grow < S) {
-          vv8 = *reinterpret_cast<const bf16x8_t*>(vrow + col);
-        } else {
-          vv8 = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
-        }
-        char* vbase = reinterpret_cast<char*>(vt_lds);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          *reinterpret_cast<short*>(vbase + vtswz(col + j, row * 2)) =
-              vv8[j];
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-
-    // ---- S = Q @ K^T  (4 col-tiles of 16) -------------------------------
-    f32x4_t s_acc[4];
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-      f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-      int krow = l15 + 16 * ct;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        bf16x8_t bfrag = *reinterpret_cast<const bf16x8_t*>(
-            reinterpret_cast<char*>(k_lds) + kswz(krow, (l4 * 8 + 32 * ks) * 2));
-        acc = MFMA_BF16_16x16x32(qfrag[ks], bfrag, acc, 0, 0, 0);
-      }
-      s_acc[ct] = acc;
-    }
-    __builtin_amdgcn_s_setprio(0);
-
-    // ---- online softmax -------------------------------------------------
-    // lane holds S[row = l4*4 + r][col = l15 + 16*ct] (scaled below)
-    const bool btile = (causal && (kvbase + KVTILE > qbase)) ||
-                       (kvbase + KVTILE > S);
-    float p_new[4][4];  // [ct][r]
-    float corr[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int grow = wave_q + l4 * 4 + r;
-      float rowmax = -INFINITY;
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) {
-        float sv = s_acc[ct][r] * scale;
-        if (btile) {
-          int gcol = kvbase + l15 + 16 * ct;
-          if ((causal && gcol > grow) || gcol >= S) sv = -INFINITY;
-        }
-        s_acc[ct][r] = sv;
-        rowmax = fmaxf(rowmax, sv);
-      }
-      // reduce across the 16 lanes sharing these rows (DPP, VALU-only)
-      rowmax = row16_reduce_max(rowmax);
-      float m_new = fmaxf(m_run[r], rowmax);
-      float c = (m_run[r] == -INFINITY) ? 0.f : __expf(m_run[r] - m_new);
-      corr[r] = c;
-      float rowsum = 0.f;
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) {
-        float p = (s_acc[ct][r] == -INFINITY) ? 0.f
-                                              : __expf(s_acc[ct][r] - m_new);
-        p_new[ct][r] = p;
-        rowsum += p;
-      }
-      rowsum = row16_reduce_sum(rowsum);
-      l_run[r] = l_run[r] * c + rowsum;
-      m_run[r] = m_new;
-    }
-    // rescale O
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o_acc[dt][r] *= corr[r];
-
-    // ---- stage P (bf16) into per-wave LDS -------------------------------
-    short* pw = p_lds[wave];
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        pw[(l4 * 4 + r) * (KVTILE + P_PAD) + l15 + 16 * ct] =
-            f2bf(p_new[ct][r]);
-    // wave-local P handoff: drain the ds_writes before cross-lane ds_reads
-    // (no cross-wave barrier needed — each wave reads only its own region;
-    // the "memory" clobber pins ordering, guide §5 rule 18)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-
-    // ---- O += P @ V  ----------------------------------------------------
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8_t afrag = *reinterpret_cast<const bf16x8_t*>(
-          pw + l15 * (KVTILE + P_PAD) + l4 * 8 + 32 * ks);
-#pragma unroll
-      for (int dt = 0; dt < 8; ++dt) {
-        bf16x8_t bfrag = *reinterpret_cast<const bf16x8_t*>(
-            reinterpret_cast<char*>(vt_lds) +
-            vtswz(l15 + 16 * dt, (l4 * 8 + 32 * ks) * 2));
-        o_acc[dt] = MFMA_BF16_16x16x32(afrag, bfrag, o_acc[dt], 0, 0, 0);
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
-    __syncthreads();  // before next tile's staging overwrites K/V
-  }
-
-  // ---- epilogue: O /= l, write out + LSE --------------------------------
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    int grow = wave_q + l4 * 4 + r;
-    if (grow >= S) continue;
-    float inv_l = (l_run[r] > 0.f) ? 1.f / l_run[r] : 0.f;
-    short* orow = out + ((long long)b * S + grow) * q_row_stride + h * DHEAD;
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt)
-      orow[l15 + 16 * dt] = f2bf(o_acc[dt][r] * inv_l);
-    if (l15 == 0 && lse_out)
-      lse_out[((long long)b * Hq + h) * S + grow] =
-          m_run[r] + __logf(fmaxf(l_run[r], 1e-30f));
-  }
-}
-
 
 // ===========================================================================
 // v5: 8-wave 32x32 "swapped QK^T" forward (guide §B 8-warp ladder).
@@ -483,6 +254,7 @@ __global__ void flash_fwd_v5_kernel(
     // defer-max (guide T13): only rescale when the running max grew by more
     // than 8/ln2 (P is then bounded by e^8, which f32 accum tolerates; LSE
     // stays exact). Masked values rely on exp2(-inf)=0 — no per-value select.
+    // (-inf - -inf = NaN fails the <= too, so a still-empty lane rescales.)
     if (!__all(tmax - m_run <= 11.5416f)) {
       float m_new = fmaxf(m_run, tmax);
       float c = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - m_new);
@@ -493,12 +265,18 @@ __global__ void flash_fwd_v5_kernel(
         for (int r = 0; r < 16; ++r) ot[mt][r] *= c;
       m_run = m_new;
     }
+    // A lane whose columns were all -inf so far (left padding, a fully
+    // masked row) still has m_run = -inf, and -inf - -inf is NaN: subtract
+    // 0 instead, so those P are exp2(-inf) = 0. Only boundary / masked
+    // tiles can hold -inf; interior tiles keep the select-free path.
+    float m_sub = m_run;
+    if (btile) m_sub = (m_run == -INFINITY) ? 0.f : m_run;
     float psum = 0.f;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        float p = __builtin_amdgcn_exp2f(st[mt][r] - m_run);
+        float p = __builtin_amdgcn_exp2f(st[mt][r] - m_sub);
         st[mt][r] = p;  // P overwrites S in-register
         psum += p;
       }
@@ -572,61 +350,72 @@ __global__ void flash_fwd_v5_kernel(
   }
 }
 
+// Shared host-side contract of flash_attn_fwd / flash_attn_bwd: the kernels
+// index k and v with q's B and S and reinterpret every pointer as bf16.
+void flash_check_qkv(const at::Tensor& q, const at::Tensor& k,
+                     const at::Tensor& v, const char* who) {
+  CHECK_ARG(q, at::kBFloat16);
+  CHECK_ARG(k, at::kBFloat16);
+  CHECK_ARG(v, at::kBFloat16);
+  CHECK_ON(k, q);
+  CHECK_ON(v, q);
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, who,
+              ": q, k, v must be [B,S,H,D]");
+  const long D = q.size(3);
+  TORCH_CHECK(D == 128 || D == 64, who, ": head_dim must be 64 or 128");
+  TORCH_CHECK(q.size(1) >= 1 && q.size(2) >= 1 && k.size(2) >= 1, who,
+              ": empty sequence or head dimension");
+  TORCH_CHECK(k.size(0) == q.size(0) && k.size(1) == q.size(1) &&
+                  k.size(3) == D,
+              who, ": k must be [B,S,Hk,D] with q's B, S and D");
+  TORCH_CHECK(v.sizes() == k.sizes(), who, ": v must have k's shape");
+  TORCH_CHECK(q.size(2) % k.size(2) == 0, who, ": GQA requires Hq % Hk == 0");
+}
+
+const float* flash_check_kvmask(const c10::optional<at::Tensor>& kvmask,
+                                const at::Tensor& q) {
+  if (!kvmask.has_value() || !kvmask->defined()) return nullptr;
+  TORCH_CHECK(kvmask->is_cuda() && kvmask->device() == q.device() &&
+                  kvmask->scalar_type() == at::kFloat &&
+                  kvmask->is_contiguous() &&
+                  kvmask->numel() == q.size(0) * q.size(1),
+              "kvmask must be a contiguous float [B,S] tensor on q's device");
+  return kvmask->data_ptr<float>();
+}
+
 std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k,
                                        at::Tensor v, bool causal,
                                        double scale,
                                        c10::optional<at::Tensor> kvmask) {
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous());
+  flash_check_qkv(q, k, v, "flash_attn_fwd");
   int B = q.size(0), S = q.size(1), Hq = q.size(2), D = q.size(3);
   int Hk = k.size(2);
-  TORCH_CHECK(D == 128 || D == 64,
-              "flash_attn_fwd: head_dim must be 64 or 128");
-  TORCH_CHECK(Hq % Hk == 0, "GQA requires Hq % Hk == 0");
-  const float* mp = nullptr;
-  if (kvmask.has_value() && kvmask->defined()) {
-    TORCH_CHECK(kvmask->scalar_type() == at::kFloat &&
-                kvmask->is_contiguous() && kvmask->numel() == (long)B * S,
-                "kvmask must be contiguous float [B,S]");
-    mp = kvmask->data_ptr<float>();
-  }
+  const float* mp = flash_check_kvmask(kvmask, q);
+  // scale == 0 selects the default softmax scale 1/sqrt(D)
+  const float fscale =
+      scale == 0.0 ? 1.0f / std::sqrt((float)D) : (float)scale;
   auto out = at::empty_like(q);
   auto lse = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
   auto stream = c10::hip::getCurrentHIPStream();
-  static const bool use_v4 = []() {
-    const char* e = getenv("DSAMD_ATTN_FWD_V4");
-    return e && e[0] == '1';
-  }();
-  if (use_v4 && D == 128 && !mp) {
-    dim3 grid((S + QTILE - 1) / QTILE, B * Hq);
-    hipLaunchKernelGGL(flash_fwd_kernel, grid, dim3(512), 0, stream.stream(),
+  dim3 grid((S + QT5 - 1) / QT5, B * Hq);
+  if (D == 128) {
+    hipLaunchKernelGGL(flash_fwd_v5_kernel<128>, grid, dim3(512), 0,
+                       stream.stream(),
                        reinterpret_cast<const short*>(q.data_ptr()),
                        reinterpret_cast<const short*>(k.data_ptr()),
                        reinterpret_cast<const short*>(v.data_ptr()),
                        reinterpret_cast<short*>(out.data_ptr()),
-                       lse.data_ptr<float>(), B, S, Hq, Hk, (float)scale,
+                       lse.data_ptr<float>(), mp, B, S, Hq, Hk, fscale,
                        causal ? 1 : 0);
   } else {
-    dim3 grid((S + QT5 - 1) / QT5, B * Hq);
-    if (D == 128) {
-      hipLaunchKernelGGL(flash_fwd_v5_kernel<128>, grid, dim3(512), 0,
-                         stream.stream(),
-                         reinterpret_cast<const short*>(q.data_ptr()),
-                         reinterpret_cast<const short*>(k.data_ptr()),
-                         reinterpret_cast<const short*>(v.data_ptr()),
-                         reinterpret_cast<short*>(out.data_ptr()),
-                         lse.data_ptr<float>(), mp, B, S, Hq, Hk,
-                         (float)scale, causal ? 1 : 0);
-    } else {
-      hipLaunchKernelGGL(flash_fwd_v5_kernel<64>, grid, dim3(512), 0,
-                         stream.stream(),
-                         reinterpret_cast<const short*>(q.data_ptr()),
-                         reinterpret_cast<const short*>(k.data_ptr()),
-                         reinterpret_cast<const short*>(v.data_ptr()),
-                         reinterpret_cast<short*>(out.data_ptr()),
-                         lse.data_ptr<float>(), mp, B, S, Hq, Hk,
-                         (float)scale, causal ? 1 : 0);
-    }
+    hipLaunchKernelGGL(flash_fwd_v5_kernel<64>, grid, dim3(512), 0,
+                       stream.stream(),
+                       reinterpret_cast<const short*>(q.data_ptr()),
+                       reinterpret_cast<const short*>(k.data_ptr()),
+                       reinterpret_cast<const short*>(v.data_ptr()),
+                       reinterpret_cast<short*>(out.data_ptr()),
+                       lse.data_ptr<float>(), mp, B, S, Hq, Hk, fscale,
+                       causal ? 1 : 0);
   }
   HIP_CHECK_KERNEL();
   return {out, lse};

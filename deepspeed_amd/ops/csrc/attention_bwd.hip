@@ -211,6 +211,9 @@ __global__ void flash_bwd_dkv_kernel(
     for (int ct = 0; ct < 2; ++ct) {
       int gq = qb + l15 + 16 * ct;
       float l = (gq < S) ? lsep[gq] : 0.f;
+      // a row with no admissible column has lse = -inf: subtracting +inf
+      // instead makes its P exp(-inf) = 0, not exp(-inf - -inf) = NaN
+      if (l == -INFINITY) l = INFINITY;
       float dr = (gq < S) ? drp[gq] : 0.f;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -325,6 +328,8 @@ __global__ void flash_bwd_dq_kernel(
   for (int r = 0; r < 4; ++r) {
     int grow = wave_q + l4 * 4 + r;
     lse_r[r] = grow < S ? lsep[grow] : 0.f;
+    // row with no admissible column (lse = -inf): P = exp(s - inf) = 0
+    if (lse_r[r] == -INFINITY) lse_r[r] = INFINITY;
     dr_r[r] = grow < S ? drp[grow] : 0.f;
   }
 
@@ -481,33 +486,42 @@ static void launch_bwd(at::Tensor& q, at::Tensor& k, at::Tensor& v,
   HIP_CHECK_KERNEL();
 }
 
+void flash_check_qkv(const at::Tensor& q, const at::Tensor& k,
+                     const at::Tensor& v, const char* who);
+const float* flash_check_kvmask(const c10::optional<at::Tensor>& kvmask,
+                                const at::Tensor& q);
+
 std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
                                        at::Tensor v, at::Tensor dout,
                                        at::Tensor out, at::Tensor lse,
                                        bool causal, double scale,
                                        c10::optional<at::Tensor> kvmask) {
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous() &&
-              dout.is_contiguous() && out.is_contiguous());
+  flash_check_qkv(q, k, v, "flash_attn_bwd");
+  CHECK_ARG(dout, at::kBFloat16);
+  CHECK_ARG(out, at::kBFloat16);
+  CHECK_ARG(lse, at::kFloat);
+  CHECK_ON(dout, q);
+  CHECK_ON(out, q);
+  CHECK_ON(lse, q);
+  TORCH_CHECK(dout.sizes() == q.sizes() && out.sizes() == q.sizes(),
+              "flash_attn_bwd: dout and out must have q's shape");
   int B = q.size(0), S = q.size(1), Hq = q.size(2), D = q.size(3);
   int Hk = k.size(2);
-  TORCH_CHECK(D == 128 || D == 64,
-              "flash_attn_bwd: head_dim must be 64 or 128");
-  const float* mp = nullptr;
-  if (kvmask.has_value() && kvmask->defined()) {
-    TORCH_CHECK(kvmask->scalar_type() == at::kFloat &&
-                kvmask->is_contiguous() && kvmask->numel() == (long)B * S,
-                "kvmask must be contiguous float [B,S]");
-    mp = kvmask->data_ptr<float>();
-  }
+  TORCH_CHECK(lse.dim() == 3 && lse.size(0) == B && lse.size(1) == Hq &&
+                  lse.size(2) == S,
+              "flash_attn_bwd: lse must be [B,Hq,S]");
+  const float* mp = flash_check_kvmask(kvmask, q);
+  // scale == 0 selects the default softmax scale 1/sqrt(D), as in forward
+  const float fscale =
+      scale == 0.0 ? 1.0f / std::sqrt((float)D) : (float)scale;
   auto dq = at::empty_like(q);
   auto dk = at::empty_like(k);
   auto dv = at::empty_like(v);
   if (D == 128)
     launch_bwd<128>(q, k, v, dout, out, lse, dq, dk, dv, mp, B, S, Hq, Hk,
-                    (float)scale, causal ? 1 : 0);
+                    fscale, causal ? 1 : 0);
   else
     launch_bwd<64>(q, k, v, dout, out, lse, dq, dk, dv, mp, B, S, Hq, Hk,
-                   (float)scale, causal ? 1 : 0);
+                   fscale, causal ? 1 : 0);
   return {dq, dk, dv};
 }

@@ -127,6 +127,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dequantize_fp_em", &dequantize_fp_em, py::arg("q"),
         py::arg("scales"), py::arg("qbits"), py::arg("group"),
         py::arg("shape"));
+  // scale = 0.0 (the default) means 1/sqrt(head_dim) in both entry points;
+  // any other value is used as given.
   m.def("flash_attn_fwd", &flash_attn_fwd, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("causal") = true, py::arg("scale") = 0.0,
         py::arg("kvmask") = c10::nullopt);

@@ -22,32 +22,46 @@ using bf16x8_t = __attribute__((ext_vector_type(8))) short;
 namespace fp8q {
 
 // ---- amax -----------------------------------------------------------------
+// max over |x| taken on the bf16 BIT patterns with the sign cleared: for
+// non-negative floats the integer order is the float order, +inf sorts above
+// every finite value and every NaN pattern above +inf, so a NaN anywhere in
+// x comes out as NaN (fmaxf would drop it). `head` elements before the first
+// 16-byte-aligned address and the tail after the last full vector are read
+// one by one.
 __global__ void amax_bf16_kernel(const short* __restrict__ x, long long n,
+                                 long long head,
                                  unsigned int* __restrict__ out) {
   long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 8;
   long long stride = (long long)gridDim.x * blockDim.x * 8;
-  float m = 0.f;
-  for (long long i = i0; i + 8 <= n; i += stride) {
-    bf16x8_t v = *reinterpret_cast<const bf16x8_t*>(x + i);
+  const long long nv = (n - head) & ~7LL;  // elements in full vectors
+  unsigned int m = 0;
+  for (long long i = i0; i < nv; i += stride) {
+    bf16x8_t v = *reinterpret_cast<const bf16x8_t*>(x + head + i);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(bf2f(v[j])));
+    for (int j = 0; j < 8; ++j) m = max(m, (unsigned int)(v[j] & 0x7fff));
   }
-  // tail (n is 8-aligned for all callers, but stay safe)
-  if (i0 == 0)
-    for (long long i = n & ~7LL; i < n; ++i)
-      m = fmaxf(m, fabsf(bf2f(x[i])));
-  m = wave_reduce_max(m);
+  if (i0 == 0) {
+    for (long long i = 0; i < head; ++i)
+      m = max(m, (unsigned int)(x[i] & 0x7fff));
+    for (long long i = head + nv; i < n; ++i)
+      m = max(m, (unsigned int)(x[i] & 0x7fff));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    m = max(m, (unsigned int)__shfl_down((int)m, off, WAVE));
   if ((threadIdx.x & 63) == 0)
-    atomicMax(out, __float_as_uint(m));  // valid: all values >= 0
+    atomicMax(out, m << 16);  // bf16 bits -> fp32 bits of the same value
 }
 
 // ---- packed convert helpers ----------------------------------------------
 template <bool E5M2>
 DEV_INLINE unsigned int cvt4(float a, float b, float c, float d, float fmax) {
-  a = fminf(fmaxf(a, -fmax), fmax);
-  b = fminf(fmaxf(b, -fmax), fmax);
-  c = fminf(fmaxf(c, -fmax), fmax);
-  d = fminf(fmaxf(d, -fmax), fmax);
+  // saturate (+-inf included); fminf/fmaxf would turn NaN into -fmax, so
+  // NaN bypasses the clamp and converts to the format's NaN
+  a = (a != a) ? a : fminf(fmaxf(a, -fmax), fmax);
+  b = (b != b) ? b : fminf(fmaxf(b, -fmax), fmax);
+  c = (c != c) ? c : fminf(fmaxf(c, -fmax), fmax);
+  d = (d != d) ? d : fminf(fmaxf(d, -fmax), fmax);
   int lo, w;
   if (E5M2) {
     lo = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, 0, false);
@@ -83,7 +97,10 @@ __global__ void fp8_cast_kernel(const short* __restrict__ x,
 
 // ---- cast + transpose -----------------------------------------------------
 // x[M,K] bf16 -> y[M,K] fp8 row-major AND yt[K,M] fp8. 64x64 tiles staged
-// as bytes in LDS (pad 4 per row spreads the column reads).
+// as bytes in LDS (pad 4 per row spreads the column reads). The 16-byte
+// vector accesses need every row start aligned: xvec (x rows, K % 8 == 0),
+// yvec (y rows, K % 16 == 0), ytvec (yt rows, M % 16 == 0); otherwise that
+// side goes element by element.
 constexpr int TDIM = 64;
 constexpr int TPAD = 4;
 
@@ -94,7 +111,8 @@ __global__ void fp8_cast_transpose_kernel(const short* __restrict__ x,
                                           unsigned char* __restrict__ yt,
                                           int M, int K,
                                           const float* __restrict__ scale,
-                                          float fmax) {
+                                          float fmax, bool xvec, bool yvec,
+                                          bool ytvec) {
   __shared__ unsigned char tile[TDIM][TDIM + TPAD];
   const float inv = 1.f / fmaxf(*scale, 1e-12f);
   const int tm = blockIdx.x * TDIM;  // row tile origin
@@ -108,7 +126,7 @@ __global__ void fp8_cast_transpose_kernel(const short* __restrict__ x,
       const short* src = x + (long long)gr * K + tk + c0;
       unsigned int w[4];
       int avail = K - (tk + c0);  // >=16 except ragged edge
-      if (avail >= 16) {
+      if (xvec && avail >= 16) {
         bf16x8_t v0 = *reinterpret_cast<const bf16x8_t*>(src);
         bf16x8_t v1 = *reinterpret_cast<const bf16x8_t*>(src + 8);
         w[0] = cvt4<E5M2>(bf2f(v0[0]) * inv, bf2f(v0[1]) * inv,
@@ -128,7 +146,7 @@ __global__ void fp8_cast_transpose_kernel(const short* __restrict__ x,
         }
         memcpy(w, tmp, 16);
       }
-      if (tk + c0 + 16 <= K) {
+      if (yvec && tk + c0 + 16 <= K) {
         *reinterpret_cast<uint4*>(y + (long long)gr * K + tk + c0) =
             *reinterpret_cast<uint4*>(w);
       } else {
@@ -154,7 +172,7 @@ __global__ void fp8_cast_transpose_kernel(const short* __restrict__ x,
       unsigned char out[16];
 #pragma unroll
       for (int j = 0; j < 16; ++j) out[j] = tile[r0 + j][c];
-      if (tm + r0 + 16 <= M) {
+      if (ytvec && tm + r0 + 16 <= M) {
         *reinterpret_cast<uint4*>(yt + (long long)gc * M + tm + r0) =
             *reinterpret_cast<uint4*>(out);
       } else {
@@ -168,24 +186,37 @@ __global__ void fp8_cast_transpose_kernel(const short* __restrict__ x,
 }  // namespace fp8q
 
 at::Tensor fp8_amax(at::Tensor x) {
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_contiguous());
+  CHECK_ARG(x, at::kBFloat16);
   auto out = at::zeros({1}, x.options().dtype(at::kFloat));
   long long n = x.numel();
+  if (n == 0) return out;
+  // elements before the first 16-byte boundary (bf16 is 2-byte aligned)
+  long long head = (16 - reinterpret_cast<uintptr_t>(x.data_ptr()) % 16) % 16 / 2;
+  head = std::min(head, n);
   auto stream = c10::hip::getCurrentHIPStream();
   int blocks = (int)std::min<long long>(4096, (n / 8 + 255) / 256);
   hipLaunchKernelGGL(fp8q::amax_bf16_kernel, dim3(std::max(blocks, 1)),
                      dim3(256), 0, stream.stream(),
-                     reinterpret_cast<const short*>(x.data_ptr()), n,
+                     reinterpret_cast<const short*>(x.data_ptr()), n, head,
                      reinterpret_cast<unsigned int*>(out.data_ptr()));
   HIP_CHECK_KERNEL();
   return out;
 }
 
+static void check_fp8_scale(const at::Tensor& scale, const at::Tensor& x) {
+  CHECK_ARG(scale, at::kFloat);
+  CHECK_ON(scale, x);
+  TORCH_CHECK(scale.numel() == 1, "scale must hold one float");
+}
+
 at::Tensor fp8_cast(at::Tensor x, at::Tensor scale, bool e5m2) {
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_contiguous());
-  TORCH_CHECK(x.numel() % 8 == 0, "fp8_cast: numel must be 8-aligned");
+  CHECK_ARG(x, at::kBFloat16);
+  check_fp8_scale(scale, x);
+  TORCH_CHECK(x.numel() % 8 == 0 && ptr_aligned(x.data_ptr(), 16),
+              "fp8_cast: numel must be 8-aligned and x 16-byte aligned");
   auto y = at::empty_like(x, x.options().dtype(at::kByte));
   long long n = x.numel();
+  if (n == 0) return y;
   auto stream = c10::hip::getCurrentHIPStream();
   int blocks = (int)std::min<long long>(8192, (n / 8 + 255) / 256);
   float fmax = e5m2 ? 57344.f : 448.f;
@@ -207,11 +238,16 @@ at::Tensor fp8_cast(at::Tensor x, at::Tensor scale, bool e5m2) {
 
 std::vector<at::Tensor> fp8_cast_transpose(at::Tensor x, at::Tensor scale,
                                            bool e5m2) {
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_contiguous() &&
-              x.dim() == 2);
+  CHECK_ARG(x, at::kBFloat16);
+  check_fp8_scale(scale, x);
+  TORCH_CHECK(x.dim() == 2 && x.numel() > 0,
+              "fp8_cast_transpose: x must be a non-empty [M,K] matrix");
   int M = x.size(0), K = x.size(1);
   auto y = at::empty({M, K}, x.options().dtype(at::kByte));
   auto yt = at::empty({K, M}, x.options().dtype(at::kByte));
+  const bool xvec = K % 8 == 0 && ptr_aligned(x.data_ptr(), 16);
+  const bool yvec = K % 16 == 0 && ptr_aligned(y.data_ptr(), 16);
+  const bool ytvec = M % 16 == 0 && ptr_aligned(yt.data_ptr(), 16);
   auto stream = c10::hip::getCurrentHIPStream();
   dim3 grid((M + 63) / 64, (K + 63) / 64);
   float fmax = e5m2 ? 57344.f : 448.f;
@@ -221,14 +257,16 @@ std::vector<at::Tensor> fp8_cast_transpose(at::Tensor x, at::Tensor scale,
                        reinterpret_cast<const short*>(x.data_ptr()),
                        reinterpret_cast<unsigned char*>(y.data_ptr()),
                        reinterpret_cast<unsigned char*>(yt.data_ptr()),
-                       M, K, scale.data_ptr<float>(), fmax);
+                       M, K, scale.data_ptr<float>(), fmax, xvec, yvec,
+                       ytvec);
   else
     hipLaunchKernelGGL(fp8q::fp8_cast_transpose_kernel<false>, grid,
                        dim3(256), 0, stream.stream(),
                        reinterpret_cast<const short*>(x.data_ptr()),
                        reinterpret_cast<unsigned char*>(y.data_ptr()),
                        reinterpret_cast<unsigned char*>(yt.data_ptr()),
-                       M, K, scale.data_ptr<float>(), fmax);
+                       M, K, scale.data_ptr<float>(), fmax, xvec, yvec,
+                       ytvec);
   HIP_CHECK_KERNEL();
   return {y, yt};
 }

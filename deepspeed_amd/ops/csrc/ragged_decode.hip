@@ -208,17 +208,34 @@ __global__ void ragged_combine_kernel(const float* __restrict__ partial_out,
 
 at::Tensor ragged_decode(at::Tensor q, at::Tensor kpool, at::Tensor vpool,
                          at::Tensor rows, at::Tensor lens, long chunk) {
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.is_contiguous());
-  TORCH_CHECK(kpool.is_contiguous() && vpool.is_contiguous());
-  TORCH_CHECK(rows.scalar_type() == at::kLong &&
-              lens.scalar_type() == at::kLong);
+  CHECK_ARG(q, at::kBFloat16);
+  CHECK_ARG(kpool, at::kBFloat16);
+  CHECK_ARG(vpool, at::kBFloat16);
+  CHECK_ARG(rows, at::kLong);
+  CHECK_ARG(lens, at::kLong);
+  CHECK_ON(kpool, q);
+  CHECK_ON(vpool, q);
+  CHECK_ON(rows, q);
+  CHECK_ON(lens, q);
+  TORCH_CHECK((q.dim() == 4 && q.size(1) == 1) || q.dim() == 3,
+              "ragged_decode: q must be [n,1,Hq,D] or [n,Hq,D]");
+  TORCH_CHECK(kpool.dim() == 4 && vpool.sizes() == kpool.sizes(),
+              "ragged_decode: kpool and vpool must both be [B,Smax,Hk,D]");
+  TORCH_CHECK(chunk >= 1, "ragged_decode: chunk must be >= 1");
   int n = q.size(0);
   int Hq = q.size(-2), D = q.size(-1);
   int Smax = kpool.size(1), Hk = kpool.size(2);
+  TORCH_CHECK(n >= 1 && Hk >= 1 && kpool.size(3) == D,
+              "ragged_decode: empty batch or pool head_dim != q head_dim");
+  TORCH_CHECK(rows.numel() == n && lens.numel() == n,
+              "ragged_decode: rows and lens must have one entry per q row");
   int G = Hq / Hk;
   TORCH_CHECK(Hq % Hk == 0 && G <= ragged::MAXG, "GQA group too large");
   TORCH_CHECK(D == 128 || D == 64, "head_dim must be 64 or 128");
   long maxlen = lens.max().item<long>();
+  TORCH_CHECK(maxlen >= 1, "ragged_decode: every row is empty");
+  TORCH_CHECK(maxlen <= Smax, "ragged_decode: lens.max() = ", maxlen,
+              " exceeds the pool's Smax = ", Smax);
   int NS = (int)std::min<long>((maxlen + chunk - 1) / chunk, 64);
   int eff_chunk = (int)((maxlen + NS - 1) / NS);
   eff_chunk = (eff_chunk + 3) & ~3;

@@ -63,7 +63,7 @@ def _quant_hip(t, e5m2, transpose):
     fmax = E5M2_MAX if e5m2 else E4M3_MAX
     dt = torch.float8_e5m2 if e5m2 else torch.float8_e4m3fn
     if ext is None or not t.is_cuda or t.dtype != torch.bfloat16 \
-            or t.numel() % 8 != 0:
+            or t.numel() % 8 != 0 or t.data_ptr() % 16 != 0:
         t8, scale = _quant(t, dt, fmax)
         return t8, (_t8(t8) if transpose else None), scale
     amax = ext.fp8_amax(t)
