@@ -10,14 +10,22 @@ MI355X-native design: the KV pool is one tensor per layer
 `[max_batch, max_seq, Hk, D]` (288 GB of HBM3E holds thousands of 8B
 slots — paged/blocked KV is not needed to avoid fragmentation at this
 scale, so slot granularity keeps the layout hipGraph-friendly). Ragged
-lengths are handled with per-row RoPE positions (`positions` arg) and
-an additive length mask through SDPA; the dedicated ragged-decode HIP
-kernel (skinny GEMV + per-row KV scan) is tracked in ROADMAP.
+lengths are handled with per-row RoPE positions (`positions` arg). On the
+GPU (bf16, head_dim 64/128) decode attention runs the `ragged_decode` HIP
+kernel straight over the pool; elsewhere an additive length mask goes
+through SDPA.
+
+`fused_step=True` (opt-in) is Dynamic SplitFuse proper: every step packs
+its prefill chunks and one token per decoding request into ONE ragged
+model call, described by a `RaggedBatch` and served by the
+`ragged_prefill` HIP kernel, so the weights are read once per step.
 """
 from dataclasses import dataclass, field
 from typing import List, Optional
 
 import torch
+
+from .ragged_batch import RaggedBatch
 
 
 @dataclass
@@ -53,6 +61,7 @@ class RaggedKVCache:
         self.ragged = None      # (kpool, vpool, rows, lens) for HIP decode
         self._prefill_slot = None
         self._prefill_off = 0   # chunked (SplitFuse-style) prefill offset
+        self.fused = None       # RaggedBatch of a fused (one-call) step
         # ragged decode HIP kernel reads straight from the pool — no
         # per-token gather copies (ref inference/v2 ragged_ops role)
         from ..ops.loader import get_ext
@@ -64,6 +73,14 @@ class RaggedKVCache:
 
     # -- model-facing update ------------------------------------------------
     def update(self, k, v):
+        if self.fused is not None:           # [1, T, Hk, D] packed tokens
+            b = self.fused
+            self.k[b.tok_slot, b.tok_pos] = k[0]
+            self.v[b.tok_slot, b.tok_pos] = v[0]
+            self.lens[b.slots] = b.kv_lens
+            self.ragged = None
+            self.attn_mask = None
+            return k, v  # attention reads the pool via ragged_prefill
         if self._prefill_slot is not None:   # [1, S, Hk, D] prompt chunk
             s = self._prefill_slot
             S = k.shape[1]
@@ -107,7 +124,7 @@ class ContinuousBatchingEngine:
     """Token-level continuous batching over a native model."""
 
     def __init__(self, model, max_batch=8, max_seq=None, device=None,
-                 prefill_chunk=None, prefill_budget=None):
+                 prefill_chunk=None, prefill_budget=None, fused_step=False):
         self.model = model
         cfg = model.cfg if hasattr(model, "cfg") else model.config
         self.cfg = cfg
@@ -129,6 +146,13 @@ class ContinuousBatchingEngine:
             prefill_chunk = prefill_budget  # budget implies chunking
         self.prefill_chunk = prefill_chunk
         self.prefill_budget = prefill_budget
+        # fused_step: the step's prefill chunks and decode rows go through
+        # ONE ragged model call instead of one call per chunk plus one for
+        # the decode batch.
+        if fused_step and not prefill_chunk:
+            raise ValueError("fused_step=True needs prefill_chunk or "
+                             "prefill_budget")
+        self.fused_step = fused_step
         self.prefilling: List[Request] = []
         self.free_slots = list(range(max_batch))
         self.pending: List[Request] = []
@@ -201,6 +225,69 @@ class ContinuousBatchingEngine:
             r.generated.append(self._sample(row, r))
             self._check_done(r)
 
+    @torch.no_grad()
+    def _fused_step(self):
+        """Prefill chunks (same budget loop as the unfused path) plus one
+        token per running request, in one ragged model call."""
+        chunks = []                          # (req, pos, take)
+        budget = self.prefill_budget or self.prefill_chunk
+        i = 0
+        while i < len(self.prefilling) and budget > 0:
+            req = self.prefilling[i]
+            pos = req.prefill_pos
+            take = 0
+            # consecutive chunks of one prompt are one longer q range
+            while budget > 0 and pos + take < len(req.prompt):
+                c = min(self.prefill_chunk, len(req.prompt) - pos - take)
+                budget -= c
+                take += c
+                if self.prefill_budget is None:
+                    break  # one chunk of one request per step
+            chunks.append((req, pos, take))
+            if self.prefill_budget is None:
+                break
+            i += 1
+        active = [r for r in self.running if not r.done]
+        if not chunks and not active:
+            return
+        seqs, ids, sample = [], [], []       # sample: (req, token row)
+        t = 0
+        for req, pos, take in chunks:
+            seqs.append((req.slot, t, take, pos + take))
+            ids.append(req.prompt[pos:pos + take])
+            t += take
+            if pos + take >= len(req.prompt):
+                sample.append((req, t - 1))
+        for r in active:
+            seqs.append((r.slot, t, 1, len(r.prompt) + len(r.generated)))
+            ids.append(torch.tensor([r.generated[-1]], dtype=torch.long))
+            sample.append((r, t))
+            t += 1
+        batch = RaggedBatch(seqs, self.max_batch, self.max_seq, self.device)
+        for c in self.caches:
+            c.fused = batch
+        try:
+            input_ids = torch.cat(ids).view(1, -1).to(self.device)
+            # only rows that sample reach lm_head (none: an empty GEMM)
+            rows = torch.tensor([i for _, i in sample], dtype=torch.long,
+                                device=self.device)
+            logits = self.model(input_ids, kv_caches=self.caches,
+                                positions=batch.tok_pos.view(1, -1),
+                                logits_rows=rows)
+        finally:
+            for c in self.caches:
+                c.fused = None
+        for req, pos, take in chunks:
+            req.prefill_pos = pos + take
+            if req.prefill_pos >= len(req.prompt):
+                # by identity: Request.__eq__ would compare prompt tensors
+                self.prefilling = [r for r in self.prefilling
+                                   if r is not req]
+                self.running.append(req)
+        for i, (req, _) in enumerate(sample):
+            req.generated.append(self._sample(logits[0, i], req))
+            self._check_done(req)
+
     @staticmethod
     def _sample(logits, req):
         logits = logits.float()
@@ -234,7 +321,9 @@ class ContinuousBatchingEngine:
 
         With prefill_chunk set, at most ONE chunk of ONE prompt is
         ingested per step (bounded prefill work), interleaved with the
-        decode batch — long prompts no longer stall running decodes."""
+        decode batch — long prompts no longer stall running decodes.
+        With fused_step the same chunks and the decode rows are ONE ragged
+        model call; a prompt that completes starts decoding next step."""
         if self.prefill_chunk is None:
             while self.pending and self.free_slots:
                 req = self.pending.pop(0)
@@ -246,6 +335,9 @@ class ContinuousBatchingEngine:
                 req.slot = self.free_slots.pop()
                 req.prefill_pos = 0
                 self.prefilling.append(req)
+            if self.fused_step:
+                self._fused_step()
+                return self._retire()
             budget = self.prefill_budget or self.prefill_chunk
             while self.prefilling and budget > 0:
                 req = self.prefilling[0]
@@ -259,17 +351,22 @@ class ContinuousBatchingEngine:
         active = [r for r in self.running if not r.done]
         if active:
             self._decode(active)
+        return self._retire()
+
+    def _retire(self):
         finished = [r for r in self.running if r.done]
         for r in finished:
             self.free_slots.append(r.slot)
-            self.running.remove(r)
+        # by identity: Request.__eq__ would compare prompt tensors
+        self.running = [r for r in self.running if not r.done]
         return finished
 
     def run(self, max_steps=10000):
         """Drain all pending/running requests; returns rid -> tokens."""
         out = {}
         steps = 0
-        while (self.pending or self.running) and steps < max_steps:
+        while (self.pending or self.prefilling or self.running) \
+                and steps < max_steps:
             for r in self.step():
                 out[r.rid] = r.tokens
             steps += 1

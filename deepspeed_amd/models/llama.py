@@ -102,7 +102,14 @@ class LlamaAttention(nn.Module):
         if kv_cache is not None:
             k, v = kv_cache.update(k, v)
             rg = getattr(kv_cache, "ragged", None)
-            if rg is not None:
+            fb = getattr(kv_cache, "fused", None)
+            if fb is not None:
+                # fused serving step: packed tokens of many sequences,
+                # attention straight over the slot pool
+                from ..ops.functional import ragged_prefill_attention
+                o = ragged_prefill_attention(q[0], kv_cache.k, kv_cache.v,
+                                             fb)
+            elif rg is not None:
                 # ragged decode straight from the slot pool (no copies)
                 from ..ops.loader import get_ext
                 o = get_ext(required=True).ragged_decode(
@@ -293,9 +300,13 @@ class LlamaForCausalLM(nn.Module):
             module.weight.data.normal_(0.0, std)
 
     def forward(self, input_ids, labels=None, seq_offset=0, kv_caches=None,
-                positions=None):
+                positions=None, logits_rows=None):
         h = self.model(input_ids, seq_offset=seq_offset, kv_caches=kv_caches,
                        positions=positions)
+        if logits_rows is not None:
+            # 1-D index into the tokens of a [1,T] batch: the vocabulary
+            # GEMM runs on those rows only
+            h = h[:, logits_rows]
         logits = self.lm_head(h)
         if labels is None:
             return logits

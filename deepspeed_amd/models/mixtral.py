@@ -89,7 +89,7 @@ class MixtralForCausalLM(nn.Module):
             module.weight.data.normal_(0.0, std)
 
     def forward(self, input_ids, labels=None, seq_offset=0, kv_caches=None,
-                positions=None):
+                positions=None, logits_rows=None):
         x = self.embed_tokens(input_ids)
         S = input_ids.shape[1]
         if positions is not None:  # per-row positions (ragged decode)
@@ -109,6 +109,8 @@ class MixtralForCausalLM(nn.Module):
                 x, l_aux = layer(x, cos, sin, kv_cache=kv)
             aux_total = aux_total + l_aux
         x = self.norm(x)
+        if logits_rows is not None:  # lm_head on the sampled rows only
+            x = x[:, logits_rows]
         logits = self.lm_head(x)
         if labels is None:
             return logits

@@ -14,6 +14,8 @@ at::Tensor l2norm_sq(std::vector<at::Tensor> tensors);
 at::Tensor fp8_amax(at::Tensor x);
 at::Tensor ragged_decode(at::Tensor q, at::Tensor kpool, at::Tensor vpool,
                          at::Tensor rows, at::Tensor lens, long chunk);
+at::Tensor ragged_prefill(at::Tensor q, at::Tensor kpool, at::Tensor vpool,
+                          at::Tensor desc, long max_qlen, long max_kvlen);
 at::Tensor fp8_cast(at::Tensor x, at::Tensor scale, bool e5m2);
 std::vector<at::Tensor> fp8_cast_transpose(at::Tensor x, at::Tensor scale,
                                            bool e5m2);
@@ -107,6 +109,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ragged_decode", &ragged_decode, py::arg("q"), py::arg("kpool"),
         py::arg("vpool"), py::arg("rows"), py::arg("lens"),
         py::arg("chunk") = 512);
+  m.def("ragged_prefill", &ragged_prefill, py::arg("q"), py::arg("kpool"),
+        py::arg("vpool"), py::arg("desc"), py::arg("max_qlen"),
+        py::arg("max_kvlen"));
   m.def("fp8_cast", &fp8_cast, py::arg("x"), py::arg("scale"),
         py::arg("e5m2") = false);
   m.def("fp8_cast_transpose", &fp8_cast_transpose, py::arg("x"),

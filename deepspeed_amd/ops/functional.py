@@ -253,6 +253,46 @@ def fused_cross_entropy(logits, targets, ignore_index=-100):
                                       targets.reshape(-1), ignore_index)
 
 
+# ------------------------------------------------ ragged prefill attention
+def _ragged_prefill_torch(q, kpool, vpool, batch):
+    """Plain loop over the sequences: SDPA per sequence with an explicit
+    causal-offset mask (token j of a sequence sees pool positions
+    0..kv_len-q_len+j of its slot)."""
+    T, Hq, D = q.shape
+    G = Hq // kpool.shape[2]
+    out = torch.empty_like(q)
+    for slot, q_start, q_len, kv_len in batch.seqs:
+        qs = q[q_start:q_start + q_len].transpose(0, 1)         # [Hq,q,D]
+        ks = kpool[slot, :kv_len].transpose(0, 1)               # [Hk,kv,D]
+        vs = vpool[slot, :kv_len].transpose(0, 1)
+        if G > 1:
+            ks = ks.repeat_interleave(G, dim=0)
+            vs = vs.repeat_interleave(G, dim=0)
+        pos = torch.arange(kv_len - q_len, kv_len, device=q.device)
+        col = torch.arange(kv_len, device=q.device)
+        mask = col.view(1, -1) <= pos.view(-1, 1)               # [q,kv]
+        o = torch.nn.functional.scaled_dot_product_attention(
+            qs.unsqueeze(0), ks.unsqueeze(0), vs.unsqueeze(0),
+            attn_mask=mask)
+        out[q_start:q_start + q_len] = o[0].transpose(0, 1)
+    return out
+
+
+def ragged_prefill_attention(q, kpool, vpool, batch):
+    """Attention of one ragged serving step straight over the KV slot pool.
+
+    q [T,Hq,D] packed tokens of all sequences in `batch` (a RaggedBatch),
+    kpool/vpool [B,Smax,Hk,D] with this step's K/V rows already written.
+    Returns [T,Hq,D]. bf16 on the GPU with D in {64,128} runs the
+    `ragged_prefill` HIP kernel (no host sync); anything else the torch loop.
+    """
+    if q.is_cuda and q.dtype == torch.bfloat16 and q.shape[-1] in (64, 128):
+        ext = get_ext(required=True)
+        return ext.ragged_prefill(q.contiguous(), kpool, vpool, batch.desc,
+                                  batch.max_qlen, batch.max_kvlen)
+    return _ragged_prefill_torch(q, kpool, vpool, batch)
+
+
 def gds_handle(*a, **kw):
     """Parity stub for reference ops/aio GDS (GPUDirect Storage) builder.
 

@@ -1,5 +1,14 @@
 #!/usr/bin/env python3
-"""Continuous-batching decode throughput vs sequential generate."""
+"""Continuous-batching decode throughput vs sequential generate.
+
+SB_FUSED=1 runs the prompt-heavy workload instead: SB_NREQ prompts of
+SB_PROMPT..SB_PROMPT+192 tokens, SB_NEW new tokens each, chunked prefill
+(SB_CHUNK tokens per chunk, SB_BUDGET prompt tokens per step). The same
+requests go through the budgeted engine twice -- one model forward per
+chunk plus one per decode batch, then fused_step=True (one ragged forward
+per step) -- each after a warm-up pass, and the tok/s and the number of
+model forwards of both are printed.
+"""
 import os
 import sys
 import time
@@ -18,6 +27,56 @@ MODEL = os.environ.get("SB_MODEL", "llama-small")
 NREQ = int(os.environ.get("SB_NREQ", 16))
 NEW = int(os.environ.get("SB_NEW", 64))
 BATCH = int(os.environ.get("SB_BATCH", 8))
+# prompt-heavy workload (SB_FUSED=1)
+FUSED = int(os.environ.get("SB_FUSED", 0))
+PROMPT = int(os.environ.get("SB_PROMPT", 256))
+CHUNK = int(os.environ.get("SB_CHUNK", 64))
+BUDGET = int(os.environ.get("SB_BUDGET", 256))
+
+
+def _run_budgeted(model, prompts, fused, dev):
+    """One timed pass; returns (seconds, model forwards, engine steps)."""
+    calls = [0]
+    hook = model.register_forward_hook(
+        lambda *a: calls.__setitem__(0, calls[0] + 1))
+    cb = ContinuousBatchingEngine(model, max_batch=BATCH,
+                                  prefill_chunk=CHUNK, prefill_budget=BUDGET,
+                                  fused_step=fused)
+    for p in prompts:
+        cb.add_request(p, max_new_tokens=NEW)
+    if dev == "cuda":
+        torch.cuda.synchronize()
+    t0 = time.time()
+    steps = 0
+    while cb.pending or cb.prefilling or cb.running:
+        cb.step()
+        steps += 1
+    if dev == "cuda":
+        torch.cuda.synchronize()
+    dt = time.time() - t0
+    hook.remove()
+    cb.close()
+    return dt, calls[0], steps
+
+
+def main_fused(model, dev):
+    vocab = model.cfg.vocab_size
+    prompts = [torch.randint(0, vocab, (PROMPT + (i % 4) * 64,))
+               for i in range(NREQ)]
+    ptok = sum(len(p) for p in prompts)
+    gtok = NREQ * NEW
+    print(f"{MODEL}: {NREQ} reqs, prompts {PROMPT}..{PROMPT + 192} "
+          f"({ptok} prompt tokens) + {NEW} new tokens each; batch {BATCH}, "
+          f"chunk {CHUNK}, budget {BUDGET}")
+    res = {}
+    for name, fused in (("unfused", False), ("fused", True)):
+        _run_budgeted(model, prompts[:BATCH], fused, dev)      # warm-up
+        dt, calls, steps = _run_budgeted(model, prompts, fused, dev)
+        res[name] = dt
+        print(f"{name:8s}: {dt:6.2f} s  {gtok / dt:8.1f} generated tok/s  "
+              f"{(ptok + gtok) / dt:9.1f} total tok/s  "
+              f"{calls:5d} model forwards in {steps} steps")
+    print(f"fused / unfused throughput: {res['unfused'] / res['fused']:.2f}x")
 
 
 def main():
@@ -25,6 +84,8 @@ def main():
     dev = "cuda" if torch.cuda.is_available() else "cpu"
     dtype = torch.bfloat16 if dev == "cuda" else torch.float32
     model = LlamaForCausalLM(LLAMA_CONFIGS[MODEL]).to(dev, dtype).eval()
+    if FUSED:
+        return main_fused(model, dev)
     vocab = model.cfg.vocab_size
     prompts = [torch.randint(0, vocab, (32 + (i % 5) * 16,))
                for i in range(NREQ)]
