@@ -19,6 +19,10 @@ through SDPA.
 its prefill chunks and one token per decoding request into ONE ragged
 model call, described by a `RaggedBatch` and served by the
 `ragged_prefill` HIP kernel, so the weights are read once per step.
+
+`fused_kv_append=True` (opt-in) replaces, on the fused step and on the
+batched decode step, the eager per-row RoPE of q and k and the pool / length
+index_puts of every layer by one `ragged_rope_append` HIP launch.
 """
 from dataclasses import dataclass, field
 from typing import List, Optional
@@ -51,7 +55,8 @@ class Request:
 class RaggedKVCache:
     """One layer's slot-granular KV pool with per-slot lengths."""
 
-    def __init__(self, max_batch, max_seq, n_kv, d, dtype, device):
+    def __init__(self, max_batch, max_seq, n_kv, d, dtype, device,
+                 rope=None):
         self.k = torch.zeros(max_batch, max_seq, n_kv, d, dtype=dtype,
                              device=device)
         self.v = torch.zeros_like(self.k)
@@ -62,6 +67,11 @@ class RaggedKVCache:
         self._prefill_slot = None
         self._prefill_off = 0   # chunked (SplitFuse-style) prefill offset
         self.fused = None       # RaggedBatch of a fused (one-call) step
+        # fused_kv_append: full fp32 (cos, sin) tables [P, D/2]; the ragged
+        # steps then go through rope_append() instead of RoPE + update()
+        self.rope = rope
+        self.pos = None         # decode: position of each row's new token
+        self.new_lens = None    # decode: pos + 1, shared by all layers
         # ragged decode HIP kernel reads straight from the pool — no
         # per-token gather copies (ref inference/v2 ragged_ops role)
         from ..ops.loader import get_ext
@@ -72,6 +82,43 @@ class RaggedKVCache:
                             and get_ext(required=False) is not None)
 
     # -- model-facing update ------------------------------------------------
+    @property
+    def fuses_rope(self):
+        """True on the steps rope_append() serves: the fused step and the
+        batched decode step. Prompt prefill keeps RoPE + update()."""
+        return self.rope is not None and (
+            self.fused is not None
+            or (self._prefill_slot is None and self.rows is not None))
+
+    def rope_append(self, q, k, v):
+        """RoPE of q and k plus update() in one `ragged_rope_append` call.
+        Takes the un-rotated projections, returns (q_rot, k, v) with k/v as
+        update() returns them (unused where attention reads the pool)."""
+        from ..ops.functional import ragged_rope_append
+        cos, sin = self.rope
+        if self.fused is not None:           # [1, T, H, D] packed tokens
+            b = self.fused
+            q = ragged_rope_append(q[0], k[0], v[0], cos, sin, b.tok_slot,
+                                   b.tok_pos, self.k, self.v, self.lens)
+            self.ragged = None
+            self.attn_mask = None
+            return q.unsqueeze(0), k, v
+        rows, pos = self.rows, self.pos      # decode: [n, 1, H, D]
+        q = ragged_rope_append(q[:, 0], k[:, 0], v[:, 0], cos, sin, rows,
+                               pos, self.k, self.v, self.lens)
+        q = q.unsqueeze(1)
+        lens = self.new_lens
+        if self._use_ragged:
+            self.attn_mask = None
+            self.ragged = (self.k, self.v, rows, lens)
+            return q, k, v
+        maxlen = int(lens.max())
+        ar = torch.arange(maxlen, device=k.device)
+        valid = ar.unsqueeze(0) < lens.unsqueeze(1)          # [n, maxlen]
+        self.attn_mask = torch.where(
+            valid, 0.0, float("-inf")).view(-1, 1, 1, maxlen).float()
+        return q, self.k[rows, :maxlen], self.v[rows, :maxlen]
+
     def update(self, k, v):
         if self.fused is not None:           # [1, T, Hk, D] packed tokens
             b = self.fused
@@ -124,7 +171,8 @@ class ContinuousBatchingEngine:
     """Token-level continuous batching over a native model."""
 
     def __init__(self, model, max_batch=8, max_seq=None, device=None,
-                 prefill_chunk=None, prefill_budget=None, fused_step=False):
+                 prefill_chunk=None, prefill_budget=None, fused_step=False,
+                 fused_kv_append=False):
         self.model = model
         cfg = model.cfg if hasattr(model, "cfg") else model.config
         self.cfg = cfg
@@ -132,9 +180,26 @@ class ContinuousBatchingEngine:
         self.max_seq = max_seq or cfg.max_position_embeddings
         self.max_batch = max_batch
         dtype = next(model.parameters()).dtype
+        # fused_kv_append (opt-in): the fused step and the decode step rotate
+        # q/k and append K/V through one `ragged_rope_append` launch per
+        # layer. The tables are the model's own buffers widened to fp32 --
+        # the values the default path rotates with.
+        self.fused_kv_append = fused_kv_append
+        rope = None
+        if fused_kv_append:
+            core = next((m for m in model.modules()
+                         if hasattr(m, "rope_cos")), None)
+            if core is None:
+                raise ValueError("fused_kv_append: the model has no "
+                                 "rope_cos/rope_sin tables")
+            rope = (core.rope_cos.to(self.device).float().contiguous(),
+                    core.rope_sin.to(self.device).float().contiguous())
+            if rope[0].shape[0] < self.max_seq:
+                raise ValueError("fused_kv_append: max_seq exceeds the "
+                                 "model's RoPE table")
         self.caches = [RaggedKVCache(max_batch, self.max_seq,
                                      cfg.num_key_value_heads, cfg.head_dim,
-                                     dtype, self.device)
+                                     dtype, self.device, rope=rope)
                        for _ in range(cfg.num_hidden_layers)]
         # Dynamic SplitFuse-style scheduling (ref FastGen): bound the
         # prompt tokens processed per step so long prompts stream in
@@ -212,15 +277,21 @@ class ContinuousBatchingEngine:
     def _decode(self, active):
         rows = torch.tensor([r.slot for r in active], dtype=torch.long,
                             device=self.device)
-        for c in self.caches:
-            c.rows = rows
         last = torch.tensor([[r.generated[-1]] for r in active],
                             dtype=torch.long, device=self.device)
         positions = self.caches[0].lens[rows].view(-1, 1)
+        pos = positions.view(-1)
+        new_lens = pos + 1 if self.fused_kv_append else None
+        for c in self.caches:
+            c.rows = rows
+            c.pos = pos
+            c.new_lens = new_lens
         logits = self.model(last, kv_caches=self.caches,
                             positions=positions)
         for c in self.caches:
             c.rows = None
+            c.pos = None
+            c.new_lens = None
         for r, row in zip(active, logits[:, -1]):
             r.generated.append(self._sample(row, r))
             self._check_done(r)

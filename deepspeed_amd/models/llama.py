@@ -97,10 +97,16 @@ class LlamaAttention(nn.Module):
         k = self.k_proj(x).view(B, S, -1, d)
         v = self.v_proj(x).view(B, S, -1, d)
         # RoPE uses the caller's cos/sin slice (seq-offset aware under SP)
-        q = apply_rope(q, cos, sin)
-        k = apply_rope(k, cos, sin)
+        if getattr(kv_cache, "fuses_rope", False):
+            # ragged serving step with fused_kv_append: RoPE of q and k, the
+            # pool write and the slot lengths are one kernel launch
+            q, k, v = kv_cache.rope_append(q, k, v)
+        else:
+            q = apply_rope(q, cos, sin)
+            k = apply_rope(k, cos, sin)
+            if kv_cache is not None:
+                k, v = kv_cache.update(k, v)
         if kv_cache is not None:
-            k, v = kv_cache.update(k, v)
             rg = getattr(kv_cache, "ragged", None)
             fb = getattr(kv_cache, "fused", None)
             if fb is not None:

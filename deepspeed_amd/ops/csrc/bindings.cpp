@@ -16,6 +16,11 @@ at::Tensor ragged_decode(at::Tensor q, at::Tensor kpool, at::Tensor vpool,
                          at::Tensor rows, at::Tensor lens, long chunk);
 at::Tensor ragged_prefill(at::Tensor q, at::Tensor kpool, at::Tensor vpool,
                           at::Tensor desc, long max_qlen, long max_kvlen);
+at::Tensor ragged_rope_append(at::Tensor q, at::Tensor k, at::Tensor v,
+                              at::Tensor cos, at::Tensor sin,
+                              at::Tensor tok_slot, at::Tensor tok_pos,
+                              at::Tensor kpool, at::Tensor vpool,
+                              c10::optional<at::Tensor> lens);
 at::Tensor fp8_cast(at::Tensor x, at::Tensor scale, bool e5m2);
 std::vector<at::Tensor> fp8_cast_transpose(at::Tensor x, at::Tensor scale,
                                            bool e5m2);
@@ -112,6 +117,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ragged_prefill", &ragged_prefill, py::arg("q"), py::arg("kpool"),
         py::arg("vpool"), py::arg("desc"), py::arg("max_qlen"),
         py::arg("max_kvlen"));
+  m.def("ragged_rope_append", &ragged_rope_append, py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("cos"), py::arg("sin"),
+        py::arg("tok_slot"), py::arg("tok_pos"), py::arg("kpool"),
+        py::arg("vpool"), py::arg("lens") = c10::nullopt);
   m.def("fp8_cast", &fp8_cast, py::arg("x"), py::arg("scale"),
         py::arg("e5m2") = false);
   m.def("fp8_cast_transpose", &fp8_cast_transpose, py::arg("x"),

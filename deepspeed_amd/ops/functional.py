@@ -293,6 +293,65 @@ def ragged_prefill_attention(q, kpool, vpool, batch):
     return _ragged_prefill_torch(q, kpool, vpool, batch)
 
 
+# --------------------------------------------- ragged RoPE + KV append
+def _ragged_rope_append_torch(q, k, v, cos, sin, tok_slot, tok_pos, kpool,
+                              vpool, lens):
+    """The pieces the unfused serving path uses: `_rope_torch` with the
+    gathered table rows, then the pool and `lens` index_puts. Out-of-range
+    tokens are dropped first (a host sync on a device, only when present)."""
+    T = q.shape[0]
+    B, Smax = kpool.shape[0], kpool.shape[1]
+    limit = min(Smax, cos.shape[0])
+    ok = ((tok_slot >= 0) & (tok_slot < B)
+          & (tok_pos >= 0) & (tok_pos < limit))
+    # a sequence is one contiguous q range with its own slot
+    last = torch.ones(T, dtype=torch.bool, device=tok_slot.device)
+    last[:-1] = tok_slot[1:] != tok_slot[:-1]
+    q_rot = None
+    if not bool(ok.all()):
+        keep = ok.nonzero().squeeze(1)
+        tok_slot, tok_pos, last = tok_slot[keep], tok_pos[keep], last[keep]
+        q_rot = torch.zeros_like(q)
+        q, k, v = q[keep], k[keep], v[keep]
+    c = cos[tok_pos].float().unsqueeze(0)
+    s = sin[tok_pos].float().unsqueeze(0)
+    q_new = _rope_torch(q.unsqueeze(0), c, s, sign=1.0)[0]
+    k_rot = _rope_torch(k.unsqueeze(0), c, s, sign=1.0)[0]
+    if q_rot is None:
+        q_rot = q_new
+    else:
+        q_rot[keep] = q_new
+    kpool[tok_slot, tok_pos] = k_rot
+    vpool[tok_slot, tok_pos] = v
+    if lens is not None:
+        lens[tok_slot[last]] = tok_pos[last] + 1
+    return q_rot
+
+
+def ragged_rope_append(q, k, v, cos, sin, tok_slot, tok_pos, kpool, vpool,
+                       lens=None):
+    """RoPE of one ragged serving step fused with its KV-pool append.
+
+    q [T,Hq,D], k/v [T,Hk,D] packed tokens; cos/sin [P,D/2] fp32 full tables;
+    tok_slot/tok_pos [T] int64 (pool slot and position of each token);
+    kpool/vpool [B,Smax,Hk,D]; lens [B] int64 or None. Returns q rotated at
+    table row tok_pos[t] and writes kpool[tok_slot[t], tok_pos[t]] = rope(k[t])
+    and vpool[...] = v[t]; with `lens`, the last token of each sequence sets
+    lens[slot] = pos + 1. A token with slot outside [0,B) or pos outside
+    [0, min(Smax,P)) is skipped (nothing written, q row zero).
+
+    bf16 on the GPU runs the `ragged_rope_append` HIP kernel (one launch, no
+    host sync); anything else the torch composition.
+    """
+    if q.is_cuda and q.dtype == torch.bfloat16:
+        ext = get_ext(required=True)
+        return ext.ragged_rope_append(q.contiguous(), k.contiguous(),
+                                      v.contiguous(), cos, sin, tok_slot,
+                                      tok_pos, kpool, vpool, lens)
+    return _ragged_rope_append_torch(q, k, v, cos, sin, tok_slot, tok_pos,
+                                     kpool, vpool, lens)
+
+
 def gds_handle(*a, **kw):
     """Parity stub for reference ops/aio GDS (GPUDirect Storage) builder.
 

@@ -89,3 +89,9 @@ class InferenceBuilder(_PrebuiltBuilder):
 class SpatialInferenceBuilder(_PrebuiltBuilder):
     NAME = "spatial_inference"
     _required_syms = ("spatial_bias_add",)
+
+
+class RaggedOpsBuilder(_PrebuiltBuilder):
+    NAME = "ragged_ops"
+    _required_syms = ("ragged_decode", "ragged_prefill",
+                      "ragged_rope_append")

@@ -8,6 +8,12 @@ requests go through the budgeted engine twice -- one model forward per
 chunk plus one per decode batch, then fused_step=True (one ragged forward
 per step) -- each after a warm-up pass, and the tok/s and the number of
 model forwards of both are printed.
+
+SB_FUSED_KV=1 adds the `fused_kv_append=True` arm (one ragged_rope_append
+launch per layer instead of eager per-row RoPE plus index_puts): a third
+pass `fused_step=True, fused_kv_append=True` in the SB_FUSED workload, and
+in the default workload a warmed pair of passes, default engine then
+fused_kv_append, after the usual lines.
 """
 import os
 import sys
@@ -29,19 +35,20 @@ NEW = int(os.environ.get("SB_NEW", 64))
 BATCH = int(os.environ.get("SB_BATCH", 8))
 # prompt-heavy workload (SB_FUSED=1)
 FUSED = int(os.environ.get("SB_FUSED", 0))
+FUSED_KV = int(os.environ.get("SB_FUSED_KV", 0))
 PROMPT = int(os.environ.get("SB_PROMPT", 256))
 CHUNK = int(os.environ.get("SB_CHUNK", 64))
 BUDGET = int(os.environ.get("SB_BUDGET", 256))
 
 
-def _run_budgeted(model, prompts, fused, dev):
+def _run_budgeted(model, prompts, fused, dev, fused_kv=False):
     """One timed pass; returns (seconds, model forwards, engine steps)."""
     calls = [0]
     hook = model.register_forward_hook(
         lambda *a: calls.__setitem__(0, calls[0] + 1))
     cb = ContinuousBatchingEngine(model, max_batch=BATCH,
                                   prefill_chunk=CHUNK, prefill_budget=BUDGET,
-                                  fused_step=fused)
+                                  fused_step=fused, fused_kv_append=fused_kv)
     for p in prompts:
         cb.add_request(p, max_new_tokens=NEW)
     if dev == "cuda":
@@ -69,14 +76,37 @@ def main_fused(model, dev):
           f"({ptok} prompt tokens) + {NEW} new tokens each; batch {BATCH}, "
           f"chunk {CHUNK}, budget {BUDGET}")
     res = {}
-    for name, fused in (("unfused", False), ("fused", True)):
-        _run_budgeted(model, prompts[:BATCH], fused, dev)      # warm-up
-        dt, calls, steps = _run_budgeted(model, prompts, fused, dev)
+    arms = [("unfused", False, False), ("fused", True, False)]
+    if FUSED_KV:
+        arms.append(("fused+kv", True, True))
+    for name, fused, kv in arms:
+        _run_budgeted(model, prompts[:BATCH], fused, dev, kv)  # warm-up
+        dt, calls, steps = _run_budgeted(model, prompts, fused, dev, kv)
         res[name] = dt
         print(f"{name:8s}: {dt:6.2f} s  {gtok / dt:8.1f} generated tok/s  "
               f"{(ptok + gtok) / dt:9.1f} total tok/s  "
               f"{calls:5d} model forwards in {steps} steps")
     print(f"fused / unfused throughput: {res['unfused'] / res['fused']:.2f}x")
+    if FUSED_KV:
+        print("fused+kv / fused throughput: "
+              f"{res['fused'] / res['fused+kv']:.2f}x")
+
+
+def _run_decode(model, prompts, dev, fused_kv):
+    """One timed pass of the default (whole-prompt prefill) engine."""
+    cb = ContinuousBatchingEngine(model, max_batch=BATCH,
+                                  fused_kv_append=fused_kv)
+    if dev == "cuda":
+        torch.cuda.synchronize()
+    t0 = time.time()
+    for p in prompts:
+        cb.add_request(p, max_new_tokens=NEW)
+    cb.run()
+    if dev == "cuda":
+        torch.cuda.synchronize()
+    dt = time.time() - t0
+    cb.close()
+    return dt
 
 
 def main():
@@ -116,6 +146,16 @@ def main():
     print(f"sequential: {seq_s:6.2f} s  {tok / seq_s:8.1f} tok/s")
     print(f"continuous (batch {BATCH}): {cb_s:6.2f} s  "
           f"{tok / cb_s:8.1f} tok/s  ({seq_s / cb_s:.2f}x)")
+    if FUSED_KV:
+        # both arms warmed (the pass above warmed the default one)
+        _run_decode(model, prompts[:BATCH], dev, True)
+        res = {}
+        for name, kv in (("continuous warm", False),
+                         ("continuous +kv", True)):
+            res[name] = dt = _run_decode(model, prompts, dev, kv)
+            print(f"{name:15s}: {dt:6.2f} s  {tok / dt:8.1f} tok/s")
+        print("+kv / warm throughput: "
+              f"{res['continuous warm'] / res['continuous +kv']:.2f}x")
 
 
 if __name__ == "__main__":
