@@ -23,6 +23,12 @@ model call, described by a `RaggedBatch` and served by the
 `fused_kv_append=True` (opt-in) replaces, on the fused step and on the
 batched decode step, the eager per-row RoPE of q and k and the pool / length
 index_puts of every layer by one `ragged_rope_append` HIP launch.
+
+`kv_dtype="fp8"` (opt-in, needs `fused_kv_append=True`, head_dim 64/128)
+keeps the pool as OCP e4m3fn codes `[B, Smax, Hk, D]` plus one fp32 scale per
+(slot, position, kv head): D + 4 bytes per cached row instead of 2 D. The
+append quantizes (`ragged_rope_append_fp8`), decode and the fused step read
+codes and scales directly (`ragged_decode_fp8`, `ragged_prefill_fp8`).
 """
 from dataclasses import dataclass, field
 from typing import List, Optional
@@ -56,14 +62,34 @@ class RaggedKVCache:
     """One layer's slot-granular KV pool with per-slot lengths."""
 
     def __init__(self, max_batch, max_seq, n_kv, d, dtype, device,
-                 rope=None):
-        self.k = torch.zeros(max_batch, max_seq, n_kv, d, dtype=dtype,
+                 rope=None, fp8=False):
+        # fp8: e4m3fn codes plus one fp32 scale per (slot, position, kv head)
+        # row -- ops.functional.kv_quantize. Needs `rope` (every ragged step
+        # appends through rope_append) and head_dim 64 / 128.
+        self.fp8 = fp8
+        self.k_scale = self.v_scale = None
+        if fp8:
+            if rope is None:
+                raise ValueError("fp8 KV pool needs fused_kv_append=True")
+            if d not in (64, 128):
+                raise ValueError("fp8 KV pool: head_dim must be 64 or 128, "
+                                 f"got {d}")
+            self.k_scale = torch.ones(max_batch, max_seq, n_kv,
+                                      dtype=torch.float32, device=device)
+            self.v_scale = torch.ones_like(self.k_scale)
+        self.k = torch.zeros(max_batch, max_seq, n_kv, d,
+                             dtype=torch.uint8 if fp8 else dtype,
                              device=device)
         self.v = torch.zeros_like(self.k)
+        if fp8:                              # byte 0 is the code of 0.0
+            self.k = self.k.view(torch.float8_e4m3fn)
+            self.v = self.v.view(torch.float8_e4m3fn)
         self.lens = torch.zeros(max_batch, dtype=torch.long, device=device)
         self.rows = None        # active slot ids for this forward
         self.attn_mask = None
-        self.ragged = None      # (kpool, vpool, rows, lens) for HIP decode
+        # (kpool, vpool, rows, lens) for HIP decode; fp8: (kpool, vpool,
+        # k_scale, v_scale, rows, lens)
+        self.ragged = None
         self._prefill_slot = None
         self._prefill_off = 0   # chunked (SplitFuse-style) prefill offset
         self.fused = None       # RaggedBatch of a fused (one-call) step
@@ -94,20 +120,33 @@ class RaggedKVCache:
         """RoPE of q and k plus update() in one `ragged_rope_append` call.
         Takes the un-rotated projections, returns (q_rot, k, v) with k/v as
         update() returns them (unused where attention reads the pool)."""
-        from ..ops.functional import ragged_rope_append
+        from ..ops.functional import (ragged_rope_append,
+                                      ragged_rope_append_fp8)
         cos, sin = self.rope
+        if self.fp8:
+            def append(q, k, v, slot, pos):
+                return ragged_rope_append_fp8(
+                    q, k, v, cos, sin, slot, pos, self.k, self.v,
+                    self.k_scale, self.v_scale, self.lens)
+        else:
+            def append(q, k, v, slot, pos):
+                return ragged_rope_append(q, k, v, cos, sin, slot, pos,
+                                          self.k, self.v, self.lens)
         if self.fused is not None:           # [1, T, H, D] packed tokens
             b = self.fused
-            q = ragged_rope_append(q[0], k[0], v[0], cos, sin, b.tok_slot,
-                                   b.tok_pos, self.k, self.v, self.lens)
+            q = append(q[0], k[0], v[0], b.tok_slot, b.tok_pos)
             self.ragged = None
             self.attn_mask = None
             return q.unsqueeze(0), k, v
         rows, pos = self.rows, self.pos      # decode: [n, 1, H, D]
-        q = ragged_rope_append(q[:, 0], k[:, 0], v[:, 0], cos, sin, rows,
-                               pos, self.k, self.v, self.lens)
+        q = append(q[:, 0], k[:, 0], v[:, 0], rows, pos)
         q = q.unsqueeze(1)
         lens = self.new_lens
+        if self.fp8:    # attention reads codes and scales; off the GPU the
+            self.attn_mask = None            # fp8 op itself falls back
+            self.ragged = (self.k, self.v, self.k_scale, self.v_scale, rows,
+                           lens)
+            return q, k, v
         if self._use_ragged:
             self.attn_mask = None
             self.ragged = (self.k, self.v, rows, lens)
@@ -132,8 +171,15 @@ class RaggedKVCache:
             s = self._prefill_slot
             S = k.shape[1]
             o = self._prefill_off
-            self.k[s, o:o + S] = k[0]
-            self.v[s, o:o + S] = v[0]
+            if self.fp8:                     # not the hot path: torch ops
+                from ..ops.functional import kv_dequantize, kv_quantize
+                self.k[s, o:o + S], self.k_scale[s, o:o + S] = \
+                    kv_quantize(k[0])
+                self.v[s, o:o + S], self.v_scale[s, o:o + S] = \
+                    kv_quantize(v[0])
+            else:
+                self.k[s, o:o + S] = k[0]
+                self.v[s, o:o + S] = v[0]
             self.lens[s] = o + S
             self.ragged = None
             if o == 0:
@@ -147,6 +193,11 @@ class RaggedKVCache:
             self.attn_mask = torch.where(k_pos <= q_pos, 0.0,
                                          float("-inf")) \
                 .view(1, 1, S, total).to(torch.float32)
+            if self.fp8:
+                return (kv_dequantize(self.k[s:s + 1, :total],
+                                      self.k_scale[s:s + 1, :total], k.dtype),
+                        kv_dequantize(self.v[s:s + 1, :total],
+                                      self.v_scale[s:s + 1, :total], v.dtype))
             return (self.k[s:s + 1, :total], self.v[s:s + 1, :total])
         rows = self.rows                     # decode: [n, 1, Hk, D]
         pos = self.lens[rows]
@@ -172,7 +223,7 @@ class ContinuousBatchingEngine:
 
     def __init__(self, model, max_batch=8, max_seq=None, device=None,
                  prefill_chunk=None, prefill_budget=None, fused_step=False,
-                 fused_kv_append=False):
+                 fused_kv_append=False, kv_dtype=None):
         self.model = model
         cfg = model.cfg if hasattr(model, "cfg") else model.config
         self.cfg = cfg
@@ -197,9 +248,20 @@ class ContinuousBatchingEngine:
             if rope[0].shape[0] < self.max_seq:
                 raise ValueError("fused_kv_append: max_seq exceeds the "
                                  "model's RoPE table")
+        # kv_dtype (opt-in): None keeps the pool in the model's dtype; "fp8"
+        # stores e4m3fn codes plus a per-row fp32 scale (half the bytes per
+        # cached element, D + 4 bytes per row) and serves it with the
+        # *_fp8 ragged kernels.
+        if kv_dtype not in (None, "fp8", torch.float8_e4m3fn):
+            raise ValueError(f"kv_dtype must be None or 'fp8', got "
+                             f"{kv_dtype!r}")
+        self.kv_fp8 = kv_dtype is not None
+        if self.kv_fp8 and not fused_kv_append:
+            raise ValueError("kv_dtype='fp8' needs fused_kv_append=True")
         self.caches = [RaggedKVCache(max_batch, self.max_seq,
                                      cfg.num_key_value_heads, cfg.head_dim,
-                                     dtype, self.device, rope=rope)
+                                     dtype, self.device, rope=rope,
+                                     fp8=self.kv_fp8)
                        for _ in range(cfg.num_hidden_layers)]
         # Dynamic SplitFuse-style scheduling (ref FastGen): bound the
         # prompt tokens processed per step so long prompts stream in

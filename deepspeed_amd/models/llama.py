@@ -109,7 +109,17 @@ class LlamaAttention(nn.Module):
         if kv_cache is not None:
             rg = getattr(kv_cache, "ragged", None)
             fb = getattr(kv_cache, "fused", None)
-            if fb is not None:
+            if getattr(kv_cache, "fp8", False) and (fb is not None
+                                                    or rg is not None):
+                # fp8 slot pool: the same two steps over codes + scales
+                from ..ops import functional as Fops
+                if fb is not None:
+                    o = Fops.ragged_prefill_attention_fp8(
+                        q[0], kv_cache.k, kv_cache.v, kv_cache.k_scale,
+                        kv_cache.v_scale, fb)
+                else:
+                    o = Fops.ragged_decode_attention_fp8(q, *rg)
+            elif fb is not None:
                 # fused serving step: packed tokens of many sequences,
                 # attention straight over the slot pool
                 from ..ops.functional import ragged_prefill_attention

@@ -21,6 +21,19 @@ at::Tensor ragged_rope_append(at::Tensor q, at::Tensor k, at::Tensor v,
                               at::Tensor tok_slot, at::Tensor tok_pos,
                               at::Tensor kpool, at::Tensor vpool,
                               c10::optional<at::Tensor> lens);
+at::Tensor ragged_decode_fp8(at::Tensor q, at::Tensor kpool, at::Tensor vpool,
+                             at::Tensor k_scale, at::Tensor v_scale,
+                             at::Tensor rows, at::Tensor lens, long chunk);
+at::Tensor ragged_prefill_fp8(at::Tensor q, at::Tensor kpool,
+                              at::Tensor vpool, at::Tensor k_scale,
+                              at::Tensor v_scale, at::Tensor desc,
+                              long max_qlen, long max_kvlen);
+at::Tensor ragged_rope_append_fp8(at::Tensor q, at::Tensor k, at::Tensor v,
+                                  at::Tensor cos, at::Tensor sin,
+                                  at::Tensor tok_slot, at::Tensor tok_pos,
+                                  at::Tensor kpool, at::Tensor vpool,
+                                  at::Tensor k_scale, at::Tensor v_scale,
+                                  c10::optional<at::Tensor> lens);
 at::Tensor fp8_cast(at::Tensor x, at::Tensor scale, bool e5m2);
 std::vector<at::Tensor> fp8_cast_transpose(at::Tensor x, at::Tensor scale,
                                            bool e5m2);
@@ -121,6 +134,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k"), py::arg("v"), py::arg("cos"), py::arg("sin"),
         py::arg("tok_slot"), py::arg("tok_pos"), py::arg("kpool"),
         py::arg("vpool"), py::arg("lens") = c10::nullopt);
+  m.def("ragged_decode_fp8", &ragged_decode_fp8, py::arg("q"),
+        py::arg("kpool"), py::arg("vpool"), py::arg("k_scale"),
+        py::arg("v_scale"), py::arg("rows"), py::arg("lens"),
+        py::arg("chunk") = 512);
+  m.def("ragged_prefill_fp8", &ragged_prefill_fp8, py::arg("q"),
+        py::arg("kpool"), py::arg("vpool"), py::arg("k_scale"),
+        py::arg("v_scale"), py::arg("desc"), py::arg("max_qlen"),
+        py::arg("max_kvlen"));
+  m.def("ragged_rope_append_fp8", &ragged_rope_append_fp8, py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("cos"), py::arg("sin"),
+        py::arg("tok_slot"), py::arg("tok_pos"), py::arg("kpool"),
+        py::arg("vpool"), py::arg("k_scale"), py::arg("v_scale"),
+        py::arg("lens") = c10::nullopt);
   m.def("fp8_cast", &fp8_cast, py::arg("x"), py::arg("scale"),
         py::arg("e5m2") = false);
   m.def("fp8_cast_transpose", &fp8_cast_transpose, py::arg("x"),

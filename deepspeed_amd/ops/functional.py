@@ -295,7 +295,7 @@ def ragged_prefill_attention(q, kpool, vpool, batch):
 
 # --------------------------------------------- ragged RoPE + KV append
 def _ragged_rope_append_torch(q, k, v, cos, sin, tok_slot, tok_pos, kpool,
-                              vpool, lens):
+                              vpool, lens, put=None):
     """The pieces the unfused serving path uses: `_rope_torch` with the
     gathered table rows, then the pool and `lens` index_puts. Out-of-range
     tokens are dropped first (a host sync on a device, only when present)."""
@@ -321,8 +321,11 @@ def _ragged_rope_append_torch(q, k, v, cos, sin, tok_slot, tok_pos, kpool,
         q_rot = q_new
     else:
         q_rot[keep] = q_new
-    kpool[tok_slot, tok_pos] = k_rot
-    vpool[tok_slot, tok_pos] = v
+    if put is not None:          # fp8 pool: quantizing write
+        put(tok_slot, tok_pos, k_rot, v)
+    else:
+        kpool[tok_slot, tok_pos] = k_rot
+        vpool[tok_slot, tok_pos] = v
     if lens is not None:
         lens[tok_slot[last]] = tok_pos[last] + 1
     return q_rot
@@ -350,6 +353,141 @@ def ragged_rope_append(q, k, v, cos, sin, tok_slot, tok_pos, kpool, vpool,
                                       tok_pos, kpool, vpool, lens)
     return _ragged_rope_append_torch(q, k, v, cos, sin, tok_slot, tok_pos,
                                      kpool, vpool, lens)
+
+
+# ------------------------------------------------------ fp8 KV slot pool
+KV_FP8_MAX = 448.0          # largest finite e4m3fn value
+KV_FP8_HEAD_DIMS = (64, 128)
+
+
+def kv_quantize(x):
+    """One e4m3fn row per (..., D) row of `x`: returns (codes, scale) with
+    codes [..., D] float8_e4m3fn and scale [...] fp32, the storage format of
+    the fp8 KV slot pool:
+
+        amax  = max |x[d]|                       (exact)
+        scale = amax / 448 if amax > 0 else 1.0  (fp32, correctly rounded)
+        inv   = 1.0 / scale                      (fp32, correctly rounded)
+        code  = e4m3fn_rne(clamp(x[d] * inv, -448, 448))   (fp32 product)
+
+    The clamp matters: x * inv can round just above 448 and torch's float8
+    cast does not saturate. An all-zero row gives scale 1.0 and codes 0.
+
+    Non-finite input (not produced by the serving path): an inf in the row
+    makes scale = inf, so every element of the row reads back as NaN; a NaN
+    element without an inf makes amax NaN, scale falls back to 1.0, that
+    element gets the NaN code and the others are clamped to +-448.
+
+    This composition is what the `ragged_rope_append_fp8` kernel computes bit
+    for bit; it is the CPU fallback and the tests' reference.
+    """
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    # The two divisions go through float64: torch's fp32 division on the GPU
+    # is not correctly rounded (a scalar divisor becomes a multiply by its
+    # reciprocal), while a float64 quotient of two fp32 values rounded once
+    # more to fp32 IS the correctly rounded fp32 quotient (53 >= 2*24 + 2
+    # bits), on every device.
+    scale = torch.where(amax > 0, (amax.double() / KV_FP8_MAX).float(),
+                        torch.ones_like(amax))
+    inv = (1.0 / scale.double()).float()
+    y = (xf * inv.unsqueeze(-1)).clamp(-KV_FP8_MAX, KV_FP8_MAX)
+    return y.to(torch.float8_e4m3fn), scale
+
+
+def kv_dequantize(codes, scale, dtype=torch.float32):
+    """float(code) * scale, computed in fp32 (or in float64 when asked for,
+    where the product is exact) and returned as `dtype`."""
+    wide = torch.float64 if dtype == torch.float64 else torch.float32
+    return (codes.to(wide) * scale.to(wide).unsqueeze(-1)).to(dtype)
+
+
+def _check_kv_fp8(kpool, vpool, k_scale, v_scale):
+    if kpool.dtype != torch.float8_e4m3fn or \
+            vpool.dtype != torch.float8_e4m3fn:
+        raise ValueError("fp8 KV pool: kpool/vpool must be float8_e4m3fn")
+    if kpool.shape[-1] not in KV_FP8_HEAD_DIMS:
+        raise ValueError("fp8 KV pool: head_dim must be 64 or 128, got "
+                         f"{kpool.shape[-1]}")
+    if k_scale.shape != kpool.shape[:-1] or v_scale.shape != vpool.shape[:-1]:
+        raise ValueError("fp8 KV pool: scales must be [B,Smax,Hk]")
+
+
+def ragged_rope_append_fp8(q, k, v, cos, sin, tok_slot, tok_pos, kpool,
+                           vpool, k_scale, v_scale, lens=None):
+    """`ragged_rope_append` into the fp8 KV slot pool.
+
+    Arguments and rules as `ragged_rope_append`, except kpool/vpool
+    [B,Smax,Hk,D] float8_e4m3fn and k_scale/v_scale [B,Smax,Hk] fp32: the
+    rotated K row (rounded to q's dtype, as the bf16 pool stores it) and the V
+    row are written as `kv_quantize` codes plus scale. A skipped token writes
+    neither codes nor scales nor lens. D must be 64 or 128. Non-finite rows:
+    see `kv_quantize`.
+
+    bf16 on the GPU runs the `ragged_rope_append_fp8` HIP kernel (one launch,
+    no host sync); anything else the torch composition.
+    """
+    _check_kv_fp8(kpool, vpool, k_scale, v_scale)
+    if q.is_cuda and q.dtype == torch.bfloat16:
+        ext = get_ext(required=True)
+        return ext.ragged_rope_append_fp8(
+            q.contiguous(), k.contiguous(), v.contiguous(), cos, sin,
+            tok_slot, tok_pos, kpool, vpool, k_scale, v_scale, lens)
+    def put(slot, pos, k_rot, v_new):    # the in-range tokens only
+        for pool, scales, x in ((kpool, k_scale, k_rot),
+                                (vpool, v_scale, v_new)):
+            codes, scale = kv_quantize(x)
+            pool.view(torch.uint8)[slot, pos] = codes.view(torch.uint8)
+            scales[slot, pos] = scale
+
+    return _ragged_rope_append_torch(q, k, v, cos, sin, tok_slot, tok_pos,
+                                     kpool, vpool, lens, put=put)
+
+
+class _DecodeRows:
+    """The decode rows as the sequence list `_ragged_prefill_torch` walks."""
+
+    def __init__(self, rows, lens):
+        self.seqs = [(int(s), i, 1, int(n)) for i, (s, n) in
+                     enumerate(zip(rows.tolist(), lens.tolist())) if n > 0]
+
+
+def ragged_decode_attention_fp8(q, kpool, vpool, k_scale, v_scale, rows,
+                                lens, chunk=512):
+    """Decode attention of q [n,1,Hq,D] (or [n,Hq,D]) over the first lens[i]
+    positions of fp8 pool slot rows[i]; returns [n,1,Hq,D].
+
+    bf16 on the GPU runs the `ragged_decode_fp8` HIP kernel; anything else
+    dequantizes the pool and runs the torch loop of the prefill fallback."""
+    _check_kv_fp8(kpool, vpool, k_scale, v_scale)
+    if q.is_cuda and q.dtype == torch.bfloat16:
+        ext = get_ext(required=True)
+        return ext.ragged_decode_fp8(q.contiguous(), kpool, vpool, k_scale,
+                                     v_scale, rows, lens, chunk)
+    n, Hq, D = q.shape[0], q.shape[-2], q.shape[-1]
+    out = _ragged_prefill_torch(q.reshape(n, Hq, D),
+                                kv_dequantize(kpool, k_scale, q.dtype),
+                                kv_dequantize(vpool, v_scale, q.dtype),
+                                _DecodeRows(rows, lens))
+    out[lens.to(out.device) == 0] = 0    # an empty row is defined as 0
+    return out.view(n, 1, Hq, D)
+
+
+def ragged_prefill_attention_fp8(q, kpool, vpool, k_scale, v_scale, batch):
+    """`ragged_prefill_attention` over the fp8 KV slot pool (this step's rows
+    already appended as codes plus scales). Returns [T,Hq,D].
+
+    bf16 on the GPU runs the `ragged_prefill_fp8` HIP kernel; anything else
+    dequantizes the pool and runs the torch loop."""
+    _check_kv_fp8(kpool, vpool, k_scale, v_scale)
+    if q.is_cuda and q.dtype == torch.bfloat16:
+        ext = get_ext(required=True)
+        return ext.ragged_prefill_fp8(q.contiguous(), kpool, vpool, k_scale,
+                                      v_scale, batch.desc, batch.max_qlen,
+                                      batch.max_kvlen)
+    return _ragged_prefill_torch(q, kv_dequantize(kpool, k_scale, q.dtype),
+                                 kv_dequantize(vpool, v_scale, q.dtype),
+                                 batch)
 
 
 def gds_handle(*a, **kw):

@@ -14,6 +14,13 @@ launch per layer instead of eager per-row RoPE plus index_puts): a third
 pass `fused_step=True, fused_kv_append=True` in the SB_FUSED workload, and
 in the default workload a warmed pair of passes, default engine then
 fused_kv_append, after the usual lines.
+
+SB_KV_FP8=1 adds the fp8 KV pool arm (`kv_dtype="fp8"`, which needs
+fused_kv_append): in either workload the bf16-pool engine with
+fused_kv_append and the fp8-pool engine run back to back, SB_ROUNDS times
+(default 3) after one warm-up pass each, and the generated tok/s of both are
+printed per round and as median [min-max]. With SB_FUSED the pair is
+`fused_step=True`; otherwise the default whole-prompt engine.
 """
 import os
 import sys
@@ -36,19 +43,44 @@ BATCH = int(os.environ.get("SB_BATCH", 8))
 # prompt-heavy workload (SB_FUSED=1)
 FUSED = int(os.environ.get("SB_FUSED", 0))
 FUSED_KV = int(os.environ.get("SB_FUSED_KV", 0))
+KV_FP8 = int(os.environ.get("SB_KV_FP8", 0))
+ROUNDS = int(os.environ.get("SB_ROUNDS", 3))
 PROMPT = int(os.environ.get("SB_PROMPT", 256))
 CHUNK = int(os.environ.get("SB_CHUNK", 64))
 BUDGET = int(os.environ.get("SB_BUDGET", 256))
 
 
-def _run_budgeted(model, prompts, fused, dev, fused_kv=False):
+def _fp8_rounds(run, gtok):
+    """`run(kv_dtype)` is one timed pass returning seconds. Warm both arms,
+    then ROUNDS back-to-back pairs; generated tok/s as median [min-max]."""
+    arms = (("bf16 pool", None), ("fp8 pool", "fp8"))
+    for _, kv in arms:
+        run(kv, warm=True)
+    rates = {name: [] for name, _ in arms}
+    for rnd in range(ROUNDS):
+        for name, kv in arms:
+            rates[name].append(gtok / run(kv, warm=False))
+        print(f"round {rnd}: " + "  ".join(
+            f"{name} {rates[name][-1]:8.1f} tok/s" for name, _ in arms))
+    med = {}
+    for name, _ in arms:
+        r = sorted(rates[name])
+        med[name] = r[len(r) // 2]
+        print(f"+kv {name:9s}: {med[name]:8.1f} generated tok/s median "
+              f"[{r[0]:.1f}-{r[-1]:.1f}] over {ROUNDS} rounds")
+    print(f"fp8 pool / bf16 pool throughput: "
+          f"{med['fp8 pool'] / med['bf16 pool']:.2f}x")
+
+
+def _run_budgeted(model, prompts, fused, dev, fused_kv=False, kv_dtype=None):
     """One timed pass; returns (seconds, model forwards, engine steps)."""
     calls = [0]
     hook = model.register_forward_hook(
         lambda *a: calls.__setitem__(0, calls[0] + 1))
     cb = ContinuousBatchingEngine(model, max_batch=BATCH,
                                   prefill_chunk=CHUNK, prefill_budget=BUDGET,
-                                  fused_step=fused, fused_kv_append=fused_kv)
+                                  fused_step=fused, fused_kv_append=fused_kv,
+                                  kv_dtype=kv_dtype)
     for p in prompts:
         cb.add_request(p, max_new_tokens=NEW)
     if dev == "cuda":
@@ -90,12 +122,17 @@ def main_fused(model, dev):
     if FUSED_KV:
         print("fused+kv / fused throughput: "
               f"{res['fused'] / res['fused+kv']:.2f}x")
+    if KV_FP8:
+        _fp8_rounds(lambda kv, warm: _run_budgeted(
+            model, prompts[:BATCH] if warm else prompts, True, dev, True,
+            kv)[0], gtok)
 
 
-def _run_decode(model, prompts, dev, fused_kv):
+def _run_decode(model, prompts, dev, fused_kv, kv_dtype=None):
     """One timed pass of the default (whole-prompt prefill) engine."""
     cb = ContinuousBatchingEngine(model, max_batch=BATCH,
-                                  fused_kv_append=fused_kv)
+                                  fused_kv_append=fused_kv,
+                                  kv_dtype=kv_dtype)
     if dev == "cuda":
         torch.cuda.synchronize()
     t0 = time.time()
@@ -156,6 +193,9 @@ def main():
             print(f"{name:15s}: {dt:6.2f} s  {tok / dt:8.1f} tok/s")
         print("+kv / warm throughput: "
               f"{res['continuous warm'] / res['continuous +kv']:.2f}x")
+    if KV_FP8:
+        _fp8_rounds(lambda kv, warm: _run_decode(
+            model, prompts[:BATCH] if warm else prompts, dev, True, kv), tok)
 
 
 if __name__ == "__main__":
