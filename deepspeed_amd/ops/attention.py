@@ -5,8 +5,13 @@ in-register softmax (permlane32_swap, exp2 domain, defer-max), async
 double-buffered K staging. Measured 350 TF (B=1) / 366 TF (B=4) at
 S=4096 — faster than torch-rocm SDPA (aotriton) forward at B=1.
 Backward (csrc/attention_bwd.hip): two-pass exact flash backward from the
-saved LSE (fused Drow kernel; pass 1 accumulates dK/dV over the GQA group
-in-kernel) — faster than the SDPA backward at the training shape.
+saved LSE, no atomics, bit-reproducible. A pre-pass writes Q^T, dO^T, K^T
+(S padded to 128) and Drow once per call; both passes then stream 32-row
+steps by global_load_lds into a double buffer, take P and dS straight from
+the MFMA accumulators as the next product's operand (no LDS round trip)
+and skip the mask predicate on interior steps; pass 1 accumulates dK/dV
+over the GQA group in-kernel. Faster than the SDPA backward at the
+training shape; measurements in profiles/README.md.
 Set DSAMD_FLASH=0 to fall back to torch SDPA; a chunked-GEMM backward
 (DSAMD_FLASH_BWD=0) remains as a reference implementation.
 

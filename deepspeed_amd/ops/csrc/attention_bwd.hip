@@ -4,12 +4,42 @@
 //   pass 1 (kv-outer): dV = P^T dO ; dK = dS^T Q    — no atomics
 //   pass 2 (q-outer):  dQ = dS K                     — no atomics
 // with dS = P o (dP - Drow) * scale, dP = dO V^T, P = exp(S*scale - lse).
-// Drow = rowsum(dO o O) is precomputed by the wrapper.
+//
+// Pre-pass (bwd_preprocess, once per call): writes the transposed images
+// Q^T, dO^T [B,Hq,D,Sp] and K^T [B,Hk,D,Sp], Drow = rowsum(dO o O) and a
+// copy of lse (with -inf -> +inf, so exp(s - lse) = 0 on rows that have no
+// admissible column), both [B,Hq,Sp]. Sp is S padded to a multiple of 128 and
+// the pad is written as zeros, so every tile read of the scratch is in
+// bounds and no tile loop stores a transposed element itself.
+//
+// Both passes have the same shape: a workgroup owns 128 rows of its outer
+// index (pass 1: 8 waves x 16 keys; pass 2: 4 waves x 32 q rows) and streams
+// the other index in steps of 32.
+//   - the first two products put the OUTER index on the MFMA lane
+//     (pass 1: S = Q K^T, dP = dO V^T with the key on the lane; pass 2:
+//     S^T = K Q^T, dP^T = V dO^T with the q row on the lane). A pair of
+//     16x16 accumulator tiles, rounded to bf16, is then already the B operand
+//     of the second products (dV^T += dO^T P, dK^T += Q^T dS; dQ^T += K^T
+//     dS^T): P and dS never cross LDS. The A operand of those products comes
+//     from the transposed image with the matching k order (element j of lane
+//     group l4 is row 4*l4 + j for j < 4 and 16 + 4*l4 + j - 4 above), two
+//     8-byte LDS reads.
+//   - each step's images (row-major + transposed, and in pass 1 the step's
+//     lse / Drow) arrive by global_load_lds into a double buffer; step t+1
+//     is issued before step t's MFMAs, one barrier per step.
+//   - -Drow is the initial accumulator of dP.
+//   - steps with nothing to mask (all rows in range, below the causal
+//     diagonal, no kv mask) skip the predicate; steps fully above the
+//     diagonal skip the math.
+//   - pass 2 launches the causal-heaviest q blocks first.
+// Results are written transposed from the accumulators: 4 consecutive d per
+// lane, one 8-byte store.
 //
 // Layout conventions follow the forward kernel (attention.hip): C/D layout
 // row=(lane>>4)*4+reg, col=lane&15; A-operand lane holds A[l15][l4*8+j];
 // row-major LDS tiles use the ((row&7)<<4) XOR swizzle with pre-swizzled
-// staging; transposed tiles use pad-8 rows + a 16B-granule XOR.
+// sources; transposed tiles are [D][32] with the 16-byte granule XORed by
+// (d>>2)&3.
 // GQA: pass 1 accumulates over the q-head group in-kernel (K/V fragments
 // stay in registers across the group), writing dK/dV at [B,S,Hk,D]
 // directly — no per-q-head buffers, no wrapper reduction.
@@ -19,285 +49,430 @@
 
 using bf16x8_t = __attribute__((ext_vector_type(8))) short;
 using f32x4_t = __attribute__((ext_vector_type(4))) float;
+using u32x4_t = __attribute__((ext_vector_type(4))) unsigned int;
+using u32x2_t = __attribute__((ext_vector_type(2))) unsigned int;
 
 #define MFMA_BF16_16x16x32 __builtin_amdgcn_mfma_f32_16x16x32_bf16
 
 namespace bwd {
 
-// drow[b,h,s] = sum_d dout[b,s,h,d] * out[b,s,h,d]  (one wave per row)
+constexpr int BR = 128;   // outer rows per workgroup
+constexpr int WR = 32;    // q rows per wave, pass 2 (4 waves)
+// 16-key tiles per wave, pass 1 (8 / KTW1 waves). 2 needs 128 + 64 registers
+// for dK^T, dV^T and the K/V fragments alone: at D 128 it spills under a
+// 256-register budget and was slower at one wave per SIMD than 1 at two.
+constexpr int KTW1 = 1;
+constexpr int TS = 32;    // streamed rows per step
+constexpr int PT = 64;    // rows per pre-pass tile
+
+// two f32 -> one u32 of 2 bf16, RNE (v_cvt_pk_bf16_f32)
+DEV_INLINE unsigned int cvtpk2(float lo, float hi) {
+  unsigned short a = __builtin_bit_cast(unsigned short, (__bf16)lo);
+  unsigned short b = __builtin_bit_cast(unsigned short, (__bf16)hi);
+  return (unsigned int)a | ((unsigned int)b << 16);
+}
+
+// ---------------------------------------------------------------------------
+// PRE-PASS. grid (Sp/64, B*Hq, 3): z = 0 Q -> Q^T and lse -> lseP,
+// z = 1 dO -> dO^T and Drow, z = 2 K -> K^T (blocks past B*Hk leave).
+// ---------------------------------------------------------------------------
 template <int DH>
-__global__ void drow_kernel(const short* __restrict__ dout,
-                            const short* __restrict__ out,
-                            float* __restrict__ drow, int S, int Hq,
-                            long long n_rows) {
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  long long row = (long long)blockIdx.x * 4 + wave;  // over B*S*Hq
-  if (row >= n_rows) return;
-  const long long nbsh = (long long)S * Hq;
-  const short* a = dout + row * DH;
-  const short* b = out + row * DH;
-  // DH/2 u32 words over 64 lanes (1 word/lane at DH=128)
-  float acc = 0.f;
-  for (int w = lane; w < DH / 2; w += 64) {
-    unsigned int au = reinterpret_cast<const unsigned int*>(a)[w];
-    unsigned int bu = reinterpret_cast<const unsigned int*>(b)[w];
-    acc += bf2f((short)(au & 0xffff)) * bf2f((short)(bu & 0xffff)) +
-           bf2f((short)(au >> 16)) * bf2f((short)(bu >> 16));
+__launch_bounds__(256)
+__global__ void bwd_preprocess(
+    const short* __restrict__ q, const short* __restrict__ k,
+    const short* __restrict__ dout, const short* __restrict__ out,
+    const float* __restrict__ lse,  // [B,Hq,S]
+    short* __restrict__ qT, short* __restrict__ doT, short* __restrict__ kT,
+    float* __restrict__ drowP, float* __restrict__ lseP,  // [B,Hq,Sp]
+    int B, int S, int Sp, int Hq, int Hk) {
+  constexpr int PPR = DH / 8;  // 16-byte pieces per row
+  __shared__ unsigned int t[PT][DH / 2 + 1];
+
+  const int z = blockIdx.z;
+  const int H = (z == 2) ? Hk : Hq;
+  const int bh = blockIdx.y;
+  if (bh >= B * H) return;
+  const int b = bh / H;
+  const int h = bh % H;
+  const int s0 = blockIdx.x * PT;
+  const short* src = (z == 0) ? q : (z == 1) ? dout : k;
+  short* dst = (z == 0) ? qT : (z == 1) ? doT : kT;
+
+  for (int i = threadIdx.x; i < PT * PPR; i += 256) {
+    const int row = i / PPR;
+    const int c = i % PPR;
+    const int s = s0 + row;
+    const long long off = (((long long)b * S + s) * H + h) * DH + c * 8;
+    u32x4_t x = {0u, 0u, 0u, 0u};
+    if (s < S) x = *reinterpret_cast<const u32x4_t*>(src + off);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) t[row][c * 4 + w] = x[w];
+    if (z == 1) {
+      u32x4_t o = {0u, 0u, 0u, 0u};
+      if (s < S) o = *reinterpret_cast<const u32x4_t*>(out + off);
+      float acc = 0.f;
+#pragma unroll
+      for (int w = 0; w < 4; ++w)
+        acc += bf2f((short)(x[w] & 0xffff)) * bf2f((short)(o[w] & 0xffff)) +
+               bf2f((short)(x[w] >> 16)) * bf2f((short)(o[w] >> 16));
+#pragma unroll
+      for (int m = PPR / 2; m > 0; m >>= 1) acc += __shfl_xor(acc, m, WAVE);
+      if (c == 0) drowP[((long long)b * Hq + h) * Sp + s] = acc;
+    } else if (z == 0 && c == 0) {
+      float l = 0.f;
+      if (s < S) {
+        l = lse[((long long)b * Hq + h) * S + s];
+        // a row with no admissible column has lse = -inf: subtracting +inf
+        // instead makes its P exp(-inf) = 0, not exp(-inf - -inf) = NaN
+        if (l == -INFINITY) l = INFINITY;
+      }
+      lseP[((long long)b * Hq + h) * Sp + s] = l;
+    }
   }
-  acc = wave_reduce_sum(acc);
-  if (lane == 0) {
-    // row index [b, s, h] -> drow[b, h, s]
-    long long bb = row / nbsh;
-    long long rem = row % nbsh;
-    long long s = rem / Hq;
-    long long h = rem % Hq;
-    drow[(bb * Hq + h) * S + s] = acc;
+  __syncthreads();
+  // [D][64 s] out: 8 pieces of 16 B per d row, consecutive lanes along s
+  for (int i = threadIdx.x; i < DH * (PT / 8); i += 256) {
+    const int d = i / (PT / 8);
+    const int pc = i % (PT / 8);
+    const int sh = (d & 1) * 16;
+    unsigned int e[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) e[j] = (t[pc * 8 + j][d >> 1] >> sh) & 0xffffu;
+    u32x4_t y = {e[0] | (e[1] << 16), e[2] | (e[3] << 16),
+                 e[4] | (e[5] << 16), e[6] | (e[7] << 16)};
+    *reinterpret_cast<u32x4_t*>(dst + (((long long)b * H + h) * DH + d) * Sp +
+                                s0 + pc * 8) = y;
   }
 }
 
-// row-major [R][DH] bf16 with ((row&7)<<4) XOR
+// ---------------------------------------------------------------------------
+// LDS images of one 32-row step. Row-major [32][DH] with the ((row&7)<<4)
+// XOR; transposed [DH][32] (64-byte rows) with the granule XOR (d>>2)&3.
+// Each is DH/16 wave-segments of 1024 B (64 lanes x 16 B, LDS-linear), so
+// the swizzles are applied to the per-lane SOURCE address.
+// ---------------------------------------------------------------------------
 template <int DH>
 DEV_INLINE int rmswz(int row, int byte_off) {
   return row * (DH * 2) + (byte_off ^ ((row & 7) << 4));
 }
 
-// transposed [128][W + 8] bf16 with 16B-granule XOR on the inner index
-template <int W>
-DEV_INLINE int trswz(int d, int inner_byte) {
-  return d * ((W + 8) * 2) + (inner_byte ^ (((d >> 5) & 3) << 4));
+DEV_INLINE void lds_dma16(const short* src, char* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds(
+      reinterpret_cast<const unsigned int*>(src),
+      reinterpret_cast<unsigned int*>(lds_wave_base), 16, 0, 0);
 }
 
-DEV_INLINE short f2bf_(float f) { return f2bf(f); }
+// rows r0..r0+31 of a [*, rs] row-major tensor (rows past S-1 repeat S-1)
+template <int DH>
+DEV_INLINE void issue_rm(const short* base, long long rs, int r0, int S,
+                         char* img, int sseg, int lane) {
+  const int linear = sseg * 1024 + lane * 16;
+  const int row = linear / (DH * 2);
+  const int colbyte = linear % (DH * 2);
+  const int src_col = colbyte ^ ((row & 7) << 4);
+  const int grow = r0 + row;
+  const int srow = grow < S ? grow : S - 1;
+  lds_dma16(base + (long long)srow * rs + (src_col >> 1), img + sseg * 1024);
+}
+
+// columns c0..c0+31 of a [DH][Sp] transposed image (always inside Sp)
+template <int DH>
+DEV_INLINE void issue_tr(const short* baseT, int Sp, int c0, char* img,
+                         int sseg, int lane) {
+  const int linear = sseg * 1024 + lane * 16;
+  const int d = linear >> 6;
+  const int g = ((linear >> 4) & 3) ^ ((d >> 2) & 3);
+  lds_dma16(baseT + (long long)d * Sp + c0 + g * 8, img + sseg * 1024);
+}
+
+// A (or B) fragment, natural k order: T[row][32*ks + 8*l4 .. +7]
+template <int DH>
+DEV_INLINE bf16x8_t read_rm(const char* img, int row, int ks, int l4) {
+  return *reinterpret_cast<const bf16x8_t*>(
+      img + rmswz<DH>(row, (l4 * 8 + 32 * ks) * 2));
+}
+
+// A fragment in accumulator-pair k order: T^T[d][4*l4 .. +3, 16+4*l4 .. +3]
+DEV_INLINE bf16x8_t read_tr(const char* img, int d, int l4) {
+  const int sw = (d >> 2) & 3;
+  const char* rowp = img + d * 64 + (l4 & 1) * 8;
+  u32x2_t lo = *reinterpret_cast<const u32x2_t*>(rowp + (((l4 >> 1) ^ sw) << 4));
+  u32x2_t hi =
+      *reinterpret_cast<const u32x2_t*>(rowp + (((2 + (l4 >> 1)) ^ sw) << 4));
+  u32x4_t w = {lo[0], lo[1], hi[0], hi[1]};
+  return __builtin_bit_cast(bf16x8_t, w);
+}
+
+// two accumulator tiles (rows 0..15 and 16..31 of the summed index) -> the
+// B fragment of the next product
+DEV_INLINE bf16x8_t pack_pair(const f32x4_t& a, const f32x4_t& b) {
+  u32x4_t w = {cvtpk2(a[0], a[1]), cvtpk2(a[2], a[3]), cvtpk2(b[0], b[1]),
+               cvtpk2(b[2], b[3])};
+  return __builtin_bit_cast(bf16x8_t, w);
+}
+
+DEV_INLINE void store4(short* p, const f32x4_t& a) {
+  u32x2_t w = {cvtpk2(a[0], a[1]), cvtpk2(a[2], a[3])};
+  *reinterpret_cast<u32x2_t*>(p) = w;
+}
 
 // ---------------------------------------------------------------------------
-// PASS 1: kv-outer. Block: 4 waves x 16 kv rows = 64 kv rows; iterates q
-// tiles of 32. Computes per-(q-head) dK, dV.
+// PASS 1: kv-outer. Block: 8 / KTW waves x 16 * KTW keys = 128 keys; q steps
+// of 32 over every q head of the group. Accumulates dK^T, dV^T (d on the
+// register row, key on the lane).
 // ---------------------------------------------------------------------------
-template <int DH>
-__launch_bounds__(256, 2)
+template <int DH, int KTW>
+__launch_bounds__(512 / KTW, 1)
 __global__ void flash_bwd_dkv_kernel(
     const short* __restrict__ q,     // [B,S,Hq,D]
     const short* __restrict__ k,     // [B,S,Hk,D]
     const short* __restrict__ v,     // [B,S,Hk,D]
     const short* __restrict__ dout,  // [B,S,Hq,D]
-    const float* __restrict__ lse,   // [B,Hq,S]
-    const float* __restrict__ drow,  // [B,Hq,S]
+    const short* __restrict__ qT,    // [B,Hq,D,Sp]
+    const short* __restrict__ doT,   // [B,Hq,D,Sp]
+    const float* __restrict__ lseP,  // [B,Hq,Sp]
+    const float* __restrict__ drowP,  // [B,Hq,Sp]
     const float* __restrict__ kvmask,  // [B,S] or null
     short* __restrict__ dk,          // [B,S,Hk,D]
     short* __restrict__ dv,          // [B,S,Hk,D]
-    int B, int S, int Hq, int Hk, float scale, int causal) {
-  constexpr int QIT = 32;
-  constexpr int NKS = DH / 32;  // A-operand k-slices
-  constexpr int NDT = DH / 16;  // d-tiles
-  __shared__ short q_lds[QIT * DH];               // row-major swz
-  __shared__ short do_lds[QIT * DH];              // row-major swz
-  __shared__ short qt_lds[DH * (QIT + 8)];        // transposed
-  __shared__ short dot_lds[DH * (QIT + 8)];       // transposed
-  __shared__ short pw_lds[4][16 * (QIT + 8)];        // per-wave P^T stage
-  __shared__ short dsw_lds[4][16 * (QIT + 8)];       // per-wave dS^T stage
+    int B, int S, int Sp, int Hq, int Hk, float scale, int causal) {
+  constexpr int NKS = DH / 32;        // k-slices of the S / dP products
+  constexpr int NDT = DH / 16;        // d-tiles of dK^T / dV^T
+  constexpr int IMG = TS * DH * 2;    // bytes per image
+  constexpr int SPI = DH / 16;        // 1 KiB segments per image
+  constexpr int NW = 8 / KTW;         // waves
+  constexpr int WRK = 16 * KTW;       // keys per wave
+  constexpr int LD_OFF = 4 * IMG;     // lse[32], Drow[32]
+  constexpr int BUF = LD_OFF + 256;
+  __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int l15 = lane & 15;
   const int l4 = lane >> 4;
 
-  const int kv_block = blockIdx.x;      // 64 kv rows per block
   const int bh = blockIdx.y;            // over B * Hk (kv heads)
   const int b = bh / Hk;
   const int hk = bh % Hk;
   const int G = Hq / Hk;
-  const int kv_base = kv_block * 64;
-  const int wave_kv = kv_base + wave * 16;
+  const int kv_base = blockIdx.x * BR;  // causal: heaviest block first
+  const int wk = kv_base + wave * WRK;
 
   const long long qrs = (long long)Hq * DH;
   const long long kvrs = (long long)Hk * DH;
   const short* kp = k + ((long long)b * S) * kvrs + hk * DH;
   const short* vp = v + ((long long)b * S) * kvrs + hk * DH;
-  const float* mp = kvmask ? kvmask + (long long)b * S : nullptr;
 
-  // K/V fragments in registers (A-operand layout, DH/32 d-slices)
-  bf16x8_t kfrag[NKS], vfrag[NKS];
-  {
-    int krow = wave_kv + l15;
-    int srow = krow < S ? krow : S - 1;
+  // K/V fragments in registers (B operands: key on the lane)
+  bf16x8_t kfrag[KTW][NKS], vfrag[KTW][NKS];
+  float maskv[KTW];
+#pragma unroll
+  for (int kt = 0; kt < KTW; ++kt) {
+    const int krow = wk + 16 * kt + l15;
+    const int srow = krow < S ? krow : S - 1;
     const short* ks = kp + (long long)srow * kvrs;
     const short* vs = vp + (long long)srow * kvrs;
 #pragma unroll
     for (int ks_i = 0; ks_i < NKS; ++ks_i) {
-      kfrag[ks_i] = *reinterpret_cast<const bf16x8_t*>(ks + ks_i * 32 + l4 * 8);
-      vfrag[ks_i] = *reinterpret_cast<const bf16x8_t*>(vs + ks_i * 32 + l4 * 8);
+      kfrag[kt][ks_i] =
+          *reinterpret_cast<const bf16x8_t*>(ks + ks_i * 32 + l4 * 8);
+      vfrag[kt][ks_i] =
+          *reinterpret_cast<const bf16x8_t*>(vs + ks_i * 32 + l4 * 8);
     }
+    maskv[kt] = (kvmask && krow < S) ? kvmask[(long long)b * S + krow] : 0.f;
   }
 
-  f32x4_t dk_acc[NDT], dv_acc[NDT];
+  f32x4_t dk_acc[NDT][KTW], dv_acc[NDT][KTW];
 #pragma unroll
-  for (int dt = 0; dt < NDT; ++dt) {
-    dk_acc[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    dv_acc[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  }
+  for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+    for (int kt = 0; kt < KTW; ++kt) {
+      dk_acc[dt][kt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+      dv_acc[dt][kt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    }
 
-  const int q_start = causal ? (kv_base / QIT) * QIT : 0;
-  // accumulate over the GQA group: all q-heads sharing this kv head
-  for (int g = 0; g < G; ++g) {
-  const int h = hk * G + g;
-  const short* qp = q + ((long long)b * S) * qrs + h * DH;
-  const short* dop = dout + ((long long)b * S) * qrs + h * DH;
-  const float* lsep = lse + ((long long)b * Hq + h) * S;
-  const float* drp = drow + ((long long)b * Hq + h) * S;
-  for (int qb = q_start; qb < S; qb += QIT) {
-    // ---- stage Q/dO (row-major swizzled + transposed) ------------------
-    {
-      // DH/16 threads per row, 16 cols each (2 x bf16x8)
-      constexpr int TPR = DH / 16;
-      int row = threadIdx.x / TPR;
-      int c0 = (threadIdx.x % TPR) * 16;
-      if (row < QIT) {
-        int grow = qb + row;
-        int srow = grow < S ? grow : S - 1;
-        const short* qs = qp + (long long)srow * qrs;
-        const short* ds = dop + (long long)srow * qrs;
-        char* qb_ = reinterpret_cast<char*>(q_lds);
-        char* db_ = reinterpret_cast<char*>(do_lds);
-        char* qtb = reinterpret_cast<char*>(qt_lds);
-        char* dtb = reinterpret_cast<char*>(dot_lds);
+  const int q_start = causal ? kv_base : 0;  // multiple of 32
+  const int nq = (S - q_start + TS - 1) / TS;
+  const int total = G * nq;
+
+  // one step's loads: Q, dO row-major, Q^T, dO^T, lse/Drow
+  auto issue = [&](int g, int qb, int bufi) {
+    const int h = hk * G + g;
+    char* buf = smem + bufi * BUF;
+    const short* qp = q + ((long long)b * S) * qrs + h * DH;
+    const short* dop = dout + ((long long)b * S) * qrs + h * DH;
+    const long long toff = ((long long)b * Hq + h) * DH * Sp;
+    const long long roff = ((long long)b * Hq + h) * Sp;
 #pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-          int col = c0 + cc * 8;
-          bf16x8_t qv = *reinterpret_cast<const bf16x8_t*>(qs + col);
-          bf16x8_t dv = *reinterpret_cast<const bf16x8_t*>(ds + col);
-          *reinterpret_cast<bf16x8_t*>(qb_ + rmswz<DH>(row, col * 2)) = qv;
-          *reinterpret_cast<bf16x8_t*>(db_ + rmswz<DH>(row, col * 2)) = dv;
+    for (int sseg = wave; sseg < SPI; sseg += NW) {
+      issue_rm<DH>(qp, qrs, qb, S, buf, sseg, lane);
+      issue_rm<DH>(dop, qrs, qb, S, buf + IMG, sseg, lane);
+      issue_tr<DH>(qT + toff, Sp, qb, buf + 2 * IMG, sseg, lane);
+      issue_tr<DH>(doT + toff, Sp, qb, buf + 3 * IMG, sseg, lane);
+    }
+    if (wave == 0) {
+      const float* s = (lane < 32 ? lseP : drowP) + roff + qb + (lane & 31);
+      __builtin_amdgcn_global_load_lds(
+          reinterpret_cast<const unsigned int*>(s),
+          reinterpret_cast<unsigned int*>(buf + LD_OFF), 4, 0, 0);
+    }
+  };
+
+  int g_nx = 0, qb_nx = q_start;  // the step to issue next
+  issue(g_nx, qb_nx, 0);
+  for (int it = 0; it < total; ++it) {
+    const int qb = qb_nx;
+    // this step's loads (the only ones in flight) have landed; after the
+    // barrier every wave is also done reading the other buffer
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    qb_nx += TS;
+    if (qb_nx >= S) {
+      qb_nx = q_start;
+      ++g_nx;
+    }
+    if (it + 1 < total) issue(g_nx, qb_nx, (it + 1) & 1);
+
+    // wave-uniform: nothing admissible in this 32 x 32 strip
+    if (wk >= S || (causal && qb + TS - 1 < wk)) continue;
+    const bool interior = !kvmask && qb + TS <= S && wk + WRK <= S &&
+                          (!causal || qb >= wk + WRK - 1);
+    const char* buf = smem + (it & 1) * BUF;
+    const float* ld = reinterpret_cast<const float*>(buf + LD_OFF);
+
+    // ---- S = Q K^T ; dP - Drow = dO V^T - Drow (2 q-tiles x 2 key-tiles) --
+    f32x4_t s_acc[2][KTW], dp_acc[2][KTW], lrow[2];
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            *reinterpret_cast<short*>(qtb + trswz<QIT>(col + j, row * 2)) =
-                qv[j];
-            *reinterpret_cast<short*>(dtb + trswz<QIT>(col + j, row * 2)) =
-                dv[j];
-          }
-        }
+    for (int qt = 0; qt < 2; ++qt) {
+      lrow[qt] = *reinterpret_cast<const f32x4_t*>(ld + 16 * qt + 4 * l4);
+      f32x4_t dr = *reinterpret_cast<const f32x4_t*>(ld + 32 + 16 * qt + 4 * l4);
+#pragma unroll
+      for (int kt = 0; kt < KTW; ++kt) {
+        s_acc[qt][kt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        dp_acc[qt][kt] = -dr;
       }
     }
-    __syncthreads();
-
-    // ---- S^T = K Q^T  (strip: 16 kv x 32 q; 2 q-coltiles) --------------
-    f32x4_t st[2], dpt[2];
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-      f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-      f32x4_t acc2 = {0.f, 0.f, 0.f, 0.f};
-      int qrow = l15 + 16 * ct;
+    for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
       for (int ks_i = 0; ks_i < NKS; ++ks_i) {
-        bf16x8_t bq = *reinterpret_cast<const bf16x8_t*>(
-            reinterpret_cast<char*>(q_lds) +
-            rmswz<DH>(qrow, (l4 * 8 + 32 * ks_i) * 2));
-        bf16x8_t bd = *reinterpret_cast<const bf16x8_t*>(
-            reinterpret_cast<char*>(do_lds) +
-            rmswz<DH>(qrow, (l4 * 8 + 32 * ks_i) * 2));
-        acc = MFMA_BF16_16x16x32(kfrag[ks_i], bq, acc, 0, 0, 0);
-        acc2 = MFMA_BF16_16x16x32(vfrag[ks_i], bd, acc2, 0, 0, 0);
+        bf16x8_t aq = read_rm<DH>(buf, l15 + 16 * qt, ks_i, l4);
+        bf16x8_t ad = read_rm<DH>(buf + IMG, l15 + 16 * qt, ks_i, l4);
+#pragma unroll
+        for (int kt = 0; kt < KTW; ++kt) {
+          s_acc[qt][kt] = MFMA_BF16_16x16x32(aq, kfrag[kt][ks_i],
+                                             s_acc[qt][kt], 0, 0, 0);
+          dp_acc[qt][kt] = MFMA_BF16_16x16x32(ad, vfrag[kt][ks_i],
+                                              dp_acc[qt][kt], 0, 0, 0);
+        }
       }
-      st[ct] = acc;    // S^T[kv][q]
-      dpt[ct] = acc2;  // dP^T[kv][q] = (dO V^T)^T = V dO^T
-    }
     __builtin_amdgcn_s_setprio(0);
 
-    // ---- P^T, dS^T ------------------------------------------------------
-    short* pw = pw_lds[wave];
-    short* dw = dsw_lds[wave];
+    // ---- P, dS in place: rows q = qb+16qt+4*l4+r, column key = wk+16kt+l15
+    if (interior) {
 #pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-      int gq = qb + l15 + 16 * ct;
-      float l = (gq < S) ? lsep[gq] : 0.f;
-      // a row with no admissible column has lse = -inf: subtracting +inf
-      // instead makes its P exp(-inf) = 0, not exp(-inf - -inf) = NaN
-      if (l == -INFINITY) l = INFINITY;
-      float dr = (gq < S) ? drp[gq] : 0.f;
+      for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int gkv = wave_kv + l4 * 4 + r;
-        bool valid = gq < S && gkv < S && (!causal || gq >= gkv);
-        float sval = st[ct][r] * scale;
-        if (mp && gkv < S) sval += mp[gkv];
-        float p = valid ? __expf(sval - l) : 0.f;
-        float dsv = p * (dpt[ct][r] - dr) * scale;
-        pw[(l4 * 4 + r) * (QIT + 8) + l15 + 16 * ct] = f2bf_(p);
-        dw[(l4 * 4 + r) * (QIT + 8) + l15 + 16 * ct] = f2bf_(dsv);
-      }
+        for (int kt = 0; kt < KTW; ++kt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float p = __expf(s_acc[qt][kt][r] * scale - lrow[qt][r]);
+            s_acc[qt][kt][r] = p;
+            dp_acc[qt][kt][r] = p * dp_acc[qt][kt][r] * scale;
+          }
+    } else {
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+        for (int kt = 0; kt < KTW; ++kt) {
+          const int gkv = wk + 16 * kt + l15;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int gq = qb + 16 * qt + 4 * l4 + r;
+            const bool valid = gq < S && gkv < S && (!causal || gq >= gkv);
+            float sval = s_acc[qt][kt][r] * scale + maskv[kt];
+            float p = valid ? __expf(sval - lrow[qt][r]) : 0.f;
+            s_acc[qt][kt][r] = p;
+            dp_acc[qt][kt][r] = p * dp_acc[qt][kt][r] * scale;
+          }
+        }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    bf16x8_t pb[KTW], dsb[KTW];
+#pragma unroll
+    for (int kt = 0; kt < KTW; ++kt) {
+      pb[kt] = pack_pair(s_acc[0][kt], s_acc[1][kt]);
+      dsb[kt] = pack_pair(dp_acc[0][kt], dp_acc[1][kt]);
+    }
 
-    // ---- dV += P^T dO ; dK += dS^T Q  (8 d-tiles each) ------------------
-    bf16x8_t pa = *reinterpret_cast<const bf16x8_t*>(
-        pw + l15 * (QIT + 8) + l4 * 8);
-    bf16x8_t da = *reinterpret_cast<const bf16x8_t*>(
-        dw + l15 * (QIT + 8) + l4 * 8);
+    // ---- dV^T += dO^T P ; dK^T += Q^T dS --------------------------------
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) {
-      bf16x8_t bdo = *reinterpret_cast<const bf16x8_t*>(
-          reinterpret_cast<char*>(dot_lds) +
-          trswz<QIT>(l15 + 16 * dt, (l4 * 8) * 2));
-      bf16x8_t bq = *reinterpret_cast<const bf16x8_t*>(
-          reinterpret_cast<char*>(qt_lds) +
-          trswz<QIT>(l15 + 16 * dt, (l4 * 8) * 2));
-      dv_acc[dt] = MFMA_BF16_16x16x32(pa, bdo, dv_acc[dt], 0, 0, 0);
-      dk_acc[dt] = MFMA_BF16_16x16x32(da, bq, dk_acc[dt], 0, 0, 0);
+      bf16x8_t aqt = read_tr(buf + 2 * IMG, l15 + 16 * dt, l4);
+      bf16x8_t adt = read_tr(buf + 3 * IMG, l15 + 16 * dt, l4);
+#pragma unroll
+      for (int kt = 0; kt < KTW; ++kt) {
+        dv_acc[dt][kt] =
+            MFMA_BF16_16x16x32(adt, pb[kt], dv_acc[dt][kt], 0, 0, 0);
+        dk_acc[dt][kt] =
+            MFMA_BF16_16x16x32(aqt, dsb[kt], dk_acc[dt][kt], 0, 0, 0);
+      }
     }
     __builtin_amdgcn_s_setprio(0);
-    __syncthreads();
   }
-  }  // group loop
 
-  // ---- epilogue: write dK/dV [B,S,Hk,D] ---------------------------------
+  // ---- epilogue: lane holds d = 16dt+4*l4 .. +3 of key wk+16kt+l15 -------
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    int gkv = wave_kv + l4 * 4 + r;
+  for (int kt = 0; kt < KTW; ++kt) {
+    const int gkv = wk + 16 * kt + l15;
     if (gkv >= S) continue;
-    short* dkr = dk + ((long long)b * S + gkv) * kvrs + hk * DH;
-    short* dvr = dv + ((long long)b * S + gkv) * kvrs + hk * DH;
+    short* dkr = dk + ((long long)b * S + gkv) * kvrs + hk * DH + 4 * l4;
+    short* dvr = dv + ((long long)b * S + gkv) * kvrs + hk * DH + 4 * l4;
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) {
-      dkr[l15 + 16 * dt] = f2bf_(dk_acc[dt][r]);
-      dvr[l15 + 16 * dt] = f2bf_(dv_acc[dt][r]);
+      store4(dkr + 16 * dt, dk_acc[dt][kt]);
+      store4(dvr + 16 * dt, dv_acc[dt][kt]);
     }
   }
 }
 
 // ---------------------------------------------------------------------------
-// PASS 2: q-outer. Block: 4 waves x 16 q rows = 64; iterates kv tiles of 64.
+// PASS 2: q-outer. Block: 4 waves x 32 q rows = 128; kv steps of 32.
+// Accumulates dQ^T (d on the register row, q on the lane).
 // ---------------------------------------------------------------------------
 template <int DH>
 __launch_bounds__(256, 2)
 __global__ void flash_bwd_dq_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, const short* __restrict__ dout,
-    const float* __restrict__ lse, const float* __restrict__ drow,
+    const short* __restrict__ kT,     // [B,Hk,D,Sp]
+    const float* __restrict__ lseP,   // [B,Hq,Sp]
+    const float* __restrict__ drowP,  // [B,Hq,Sp]
     const float* __restrict__ kvmask,  // [B,S] or null
     short* __restrict__ dq,  // [B,S,Hq,D]
-    int B, int S, int Hq, int Hk, float scale, int causal) {
-  constexpr int KVT = 64;
+    int B, int S, int Sp, int Hq, int Hk, float scale, int causal) {
   constexpr int NKS = DH / 32;
   constexpr int NDT = DH / 16;
-  __shared__ short k_lds[KVT * DH];          // row-major swz
-  __shared__ short v_lds[KVT * DH];          // row-major swz
-  __shared__ short kt_lds[DH * (KVT + 8)];   // transposed
-  __shared__ short dsw_lds[4][16 * (KVT + 8)];  // per-wave dS stage
+  constexpr int IMG = TS * DH * 2;
+  constexpr int SPI = DH / 16;
+  constexpr int IPI = SPI / 4;
+  constexpr int BUF = 3 * IMG;  // K, V row-major, K^T
+  __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int l15 = lane & 15;
   const int l4 = lane >> 4;
 
-  const int qtile = blockIdx.x;
+  // causal: the last q block has the most kv steps; launch it first
+  const int qtile = gridDim.x - 1 - blockIdx.x;
   const int bh = blockIdx.y;
   const int b = bh / Hq;
   const int h = bh % Hq;
   const int hk = h / (Hq / Hk);
-  const int qbase = qtile * 64;
-  const int wave_q = qbase + wave * 16;
+  const int qbase = qtile * BR;
+  const int wq = qbase + wave * WR;
 
   const long long qrs = (long long)Hq * DH;
   const long long kvrs = (long long)Hk * DH;
@@ -305,141 +480,144 @@ __global__ void flash_bwd_dq_kernel(
   const short* dop = dout + ((long long)b * S) * qrs + h * DH;
   const short* kp = k + ((long long)b * S) * kvrs + hk * DH;
   const short* vp = v + ((long long)b * S) * kvrs + hk * DH;
-  const float* lsep = lse + ((long long)b * Hq + h) * S;
-  const float* drp = drow + ((long long)b * Hq + h) * S;
+  const short* ktp = kT + ((long long)b * Hk + hk) * DH * Sp;
   const float* mp = kvmask ? kvmask + (long long)b * S : nullptr;
 
-  // Q and dO fragments in registers
-  bf16x8_t qfrag[NKS], dofrag[NKS];
-  {
-    int qrow = wave_q + l15;
-    int srow = qrow < S ? qrow : S - 1;
+  // Q and dO fragments in registers (B operands: q row on the lane), and
+  // the lane's row constants (wq + 31 < Sp: the padded copies are in bounds)
+  bf16x8_t qfrag[2][NKS], dofrag[2][NKS];
+  float lse_l[2], dr_l[2];
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    const int qrow = wq + 16 * qt + l15;
+    const int srow = qrow < S ? qrow : S - 1;
     const short* qs = qp + (long long)srow * qrs;
     const short* ds = dop + (long long)srow * qrs;
 #pragma unroll
     for (int ks_i = 0; ks_i < NKS; ++ks_i) {
-      qfrag[ks_i] = *reinterpret_cast<const bf16x8_t*>(qs + ks_i * 32 + l4 * 8);
-      dofrag[ks_i] =
+      qfrag[qt][ks_i] =
+          *reinterpret_cast<const bf16x8_t*>(qs + ks_i * 32 + l4 * 8);
+      dofrag[qt][ks_i] =
           *reinterpret_cast<const bf16x8_t*>(ds + ks_i * 32 + l4 * 8);
     }
-  }
-  float lse_r[4], dr_r[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    int grow = wave_q + l4 * 4 + r;
-    lse_r[r] = grow < S ? lsep[grow] : 0.f;
-    // row with no admissible column (lse = -inf): P = exp(s - inf) = 0
-    if (lse_r[r] == -INFINITY) lse_r[r] = INFINITY;
-    dr_r[r] = grow < S ? drp[grow] : 0.f;
+    lse_l[qt] = lseP[((long long)b * Hq + h) * Sp + qrow];
+    dr_l[qt] = drowP[((long long)b * Hq + h) * Sp + qrow];
   }
 
-  f32x4_t dq_acc[NDT];
+  f32x4_t dq_acc[NDT][2];
 #pragma unroll
-  for (int dt = 0; dt < NDT; ++dt) dq_acc[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) dq_acc[dt][qt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  const int kv_end = causal ? min(S, qbase + 64) : S;
-  const int n_tiles = (kv_end + KVT - 1) / KVT;
-  for (int t = 0; t < n_tiles; ++t) {
-    const int kvb = t * KVT;
-    // ---- stage K/V row-major + Kt transposed ----------------------------
-    {
-      // DH/32 threads per row, 32 cols each (4 x bf16x8)
-      constexpr int TPR = DH / 32;
-      int row = threadIdx.x / TPR;
-      int c0 = (threadIdx.x % TPR) * 32;
-      if (row < KVT) {
-        int grow = kvb + row;
-        int srow = grow < S ? grow : S - 1;
-        const short* ks = kp + (long long)srow * kvrs;
-        const short* vs = vp + (long long)srow * kvrs;
-        char* kb_ = reinterpret_cast<char*>(k_lds);
-        char* vb_ = reinterpret_cast<char*>(v_lds);
-        char* ktb = reinterpret_cast<char*>(kt_lds);
+  const int kv_end = causal ? min(S, qbase + BR) : S;
+  const int n_tiles = (kv_end + TS - 1) / TS;
+
+  auto issue = [&](int kvb, int bufi) {
+    char* buf = smem + bufi * BUF;
 #pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
-          int col = c0 + cc * 8;
-          bf16x8_t kv8 = *reinterpret_cast<const bf16x8_t*>(ks + col);
-          bf16x8_t vv8 = *reinterpret_cast<const bf16x8_t*>(vs + col);
-          *reinterpret_cast<bf16x8_t*>(kb_ + rmswz<DH>(row, col * 2)) = kv8;
-          *reinterpret_cast<bf16x8_t*>(vb_ + rmswz<DH>(row, col * 2)) = vv8;
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            *reinterpret_cast<short*>(ktb + trswz<KVT>(col + j, row * 2)) =
-                kv8[j];
-        }
-      }
+    for (int i = 0; i < IPI; ++i) {
+      const int sseg = i * 4 + wave;
+      issue_rm<DH>(kp, kvrs, kvb, S, buf, sseg, lane);
+      issue_rm<DH>(vp, kvrs, kvb, S, buf + IMG, sseg, lane);
+      issue_tr<DH>(ktp, Sp, kvb, buf + 2 * IMG, sseg, lane);
     }
-    __syncthreads();
+  };
 
-    // ---- S = Q K^T ; dP = dO V^T  (4 kv-coltiles) -----------------------
-    f32x4_t s_acc[4], dp_acc[4];
+  issue(0, 0);
+  for (int t = 0; t < n_tiles; ++t) {
+    const int kvb = t * TS;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t + 1 < n_tiles) issue(kvb + TS, (t + 1) & 1);
+
+    // wave-uniform: nothing admissible in this 32 x 32 strip
+    if (wq >= S || (causal && kvb > wq + WR - 1)) continue;
+    const bool interior = !mp && kvb + TS <= S && wq + WR <= S &&
+                          (!causal || kvb + TS - 1 <= wq);
+    const char* buf = smem + (t & 1) * BUF;
+
+    // ---- S^T = K Q^T ; dP^T - Drow (2 key-tiles x 2 q-tiles) -------------
+    f32x4_t s_acc[2][2], dp_acc[2][2];
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) {
+        s_acc[kt][qt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        dp_acc[kt][qt] =
+            f32x4_t{-dr_l[qt], -dr_l[qt], -dr_l[qt], -dr_l[qt]};
+      }
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-      f32x4_t a1 = {0.f, 0.f, 0.f, 0.f};
-      f32x4_t a2 = {0.f, 0.f, 0.f, 0.f};
-      int krow = l15 + 16 * ct;
+    for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int ks_i = 0; ks_i < NKS; ++ks_i) {
-        bf16x8_t bk = *reinterpret_cast<const bf16x8_t*>(
-            reinterpret_cast<char*>(k_lds) +
-            rmswz<DH>(krow, (l4 * 8 + 32 * ks_i) * 2));
-        bf16x8_t bv = *reinterpret_cast<const bf16x8_t*>(
-            reinterpret_cast<char*>(v_lds) +
-            rmswz<DH>(krow, (l4 * 8 + 32 * ks_i) * 2));
-        a1 = MFMA_BF16_16x16x32(qfrag[ks_i], bk, a1, 0, 0, 0);
-        a2 = MFMA_BF16_16x16x32(dofrag[ks_i], bv, a2, 0, 0, 0);
+        bf16x8_t ak = read_rm<DH>(buf, l15 + 16 * kt, ks_i, l4);
+        bf16x8_t av = read_rm<DH>(buf + IMG, l15 + 16 * kt, ks_i, l4);
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+          s_acc[kt][qt] = MFMA_BF16_16x16x32(ak, qfrag[qt][ks_i],
+                                             s_acc[kt][qt], 0, 0, 0);
+          dp_acc[kt][qt] = MFMA_BF16_16x16x32(av, dofrag[qt][ks_i],
+                                              dp_acc[kt][qt], 0, 0, 0);
+        }
       }
-      s_acc[ct] = a1;
-      dp_acc[ct] = a2;
-    }
     __builtin_amdgcn_s_setprio(0);
 
-    // ---- dS = P o (dP - Drow) * scale -----------------------------------
-    short* dw = dsw_lds[wave];
+    // ---- dS^T in place: rows key = kvb+16kt+4*l4+r, column q = wq+16qt+l15
+    if (interior) {
 #pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
+      for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int grow = wave_q + l4 * 4 + r;
-        int gcol = kvb + l15 + 16 * ct;
-        bool valid = grow < S && gcol < S && (!causal || gcol <= grow);
-        float sval = s_acc[ct][r] * scale;
-        if (mp && gcol < S) sval += mp[gcol];
-        float p = valid ? __expf(sval - lse_r[r]) : 0.f;
-        float dsv = p * (dp_acc[ct][r] - dr_r[r]) * scale;
-        dw[(l4 * 4 + r) * (KVT + 8) + l15 + 16 * ct] = f2bf_(dsv);
-      }
+        for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float p = __expf(s_acc[kt][qt][r] * scale - lse_l[qt]);
+            dp_acc[kt][qt][r] = p * dp_acc[kt][qt][r] * scale;
+          }
+    } else {
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int gkv = kvb + 16 * kt + 4 * l4 + r;
+          const float mv = (mp && gkv < S) ? mp[gkv] : 0.f;
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt) {
+            const int gq = wq + 16 * qt + l15;
+            const bool valid = gq < S && gkv < S && (!causal || gkv <= gq);
+            float sval = s_acc[kt][qt][r] * scale + mv;
+            float p = valid ? __expf(sval - lse_l[qt]) : 0.f;
+            dp_acc[kt][qt][r] = p * dp_acc[kt][qt][r] * scale;
+          }
+        }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    bf16x8_t dsb[2];
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt)
+      dsb[qt] = pack_pair(dp_acc[0][qt], dp_acc[1][qt]);
 
-    // ---- dQ += dS K  (2 kv-slices x 8 d-tiles) --------------------------
+    // ---- dQ^T += K^T dS^T -------------------------------------------------
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int ks_i = 0; ks_i < 2; ++ks_i) {
-      bf16x8_t a = *reinterpret_cast<const bf16x8_t*>(
-          dw + l15 * (KVT + 8) + l4 * 8 + 32 * ks_i);
+    for (int dt = 0; dt < NDT; ++dt) {
+      bf16x8_t akt = read_tr(buf + 2 * IMG, l15 + 16 * dt, l4);
 #pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) {
-        bf16x8_t bkt = *reinterpret_cast<const bf16x8_t*>(
-            reinterpret_cast<char*>(kt_lds) +
-            trswz<KVT>(l15 + 16 * dt, (l4 * 8 + 32 * ks_i) * 2));
-        dq_acc[dt] = MFMA_BF16_16x16x32(a, bkt, dq_acc[dt], 0, 0, 0);
-      }
+      for (int qt = 0; qt < 2; ++qt)
+        dq_acc[dt][qt] =
+            MFMA_BF16_16x16x32(akt, dsb[qt], dq_acc[dt][qt], 0, 0, 0);
     }
     __builtin_amdgcn_s_setprio(0);
-    __syncthreads();
   }
 
-  // ---- epilogue ---------------------------------------------------------
+  // ---- epilogue: lane holds d = 16dt+4*l4 .. +3 of q row wq+16qt+l15 ------
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    int grow = wave_q + l4 * 4 + r;
-    if (grow >= S) continue;
-    short* dqr = dq + ((long long)b * S + grow) * qrs + h * DH;
+  for (int qt = 0; qt < 2; ++qt) {
+    const int gq = wq + 16 * qt + l15;
+    if (gq >= S) continue;
+    short* dqr = dq + ((long long)b * S + gq) * qrs + h * DH + 4 * l4;
 #pragma unroll
-    for (int dt = 0; dt < NDT; ++dt)
-      dqr[l15 + 16 * dt] = f2bf_(dq_acc[dt][r]);
+    for (int dt = 0; dt < NDT; ++dt) store4(dqr + 16 * dt, dq_acc[dt][qt]);
   }
 }
 
@@ -452,37 +630,38 @@ static void launch_bwd(at::Tensor& q, at::Tensor& k, at::Tensor& v,
                        const float* mp, int B, int S, int Hq, int Hk,
                        float scale, int causal) {
   auto stream = c10::hip::getCurrentHIPStream();
-  auto drow = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
-  long long rows = (long long)B * S * Hq;
-  dim3 gridd((rows + 3) / 4);
-  hipLaunchKernelGGL(bwd::drow_kernel<DH>, gridd, dim3(256), 0,
-                     stream.stream(),
-                     reinterpret_cast<const short*>(dout.data_ptr()),
-                     reinterpret_cast<const short*>(out.data_ptr()),
-                     drow.data_ptr<float>(), S, Hq, rows);
+  // scratch, fully rewritten (pad included) by the pre-pass of every call
+  const int Sp = (S + bwd::BR - 1) / bwd::BR * bwd::BR;
+  auto qT = at::empty({B, Hq, DH, Sp}, q.options());
+  auto doT = at::empty({B, Hq, DH, Sp}, q.options());
+  auto kT = at::empty({B, Hk, DH, Sp}, q.options());
+  auto drow = at::empty({B, Hq, Sp}, q.options().dtype(at::kFloat));
+  auto lseP = at::empty({B, Hq, Sp}, q.options().dtype(at::kFloat));
+  auto sp = [](const at::Tensor& t) {
+    return reinterpret_cast<const short*>(t.data_ptr());
+  };
+  auto spm = [](at::Tensor& t) {
+    return reinterpret_cast<short*>(t.data_ptr());
+  };
+  dim3 grid0(Sp / bwd::PT, B * Hq, 3);
+  hipLaunchKernelGGL(bwd::bwd_preprocess<DH>, grid0, dim3(256), 0,
+                     stream.stream(), sp(q), sp(k), sp(dout), sp(out),
+                     lse.data_ptr<float>(), spm(qT), spm(doT), spm(kT),
+                     drow.data_ptr<float>(), lseP.data_ptr<float>(), B, S,
+                     Sp, Hq, Hk);
   HIP_CHECK_KERNEL();
-  dim3 grid1((S + 63) / 64, B * Hk);
-  hipLaunchKernelGGL(bwd::flash_bwd_dkv_kernel<DH>, grid1, dim3(256), 0,
-                     stream.stream(),
-                     reinterpret_cast<const short*>(q.data_ptr()),
-                     reinterpret_cast<const short*>(k.data_ptr()),
-                     reinterpret_cast<const short*>(v.data_ptr()),
-                     reinterpret_cast<const short*>(dout.data_ptr()),
-                     lse.data_ptr<float>(), drow.data_ptr<float>(), mp,
-                     reinterpret_cast<short*>(dk.data_ptr()),
-                     reinterpret_cast<short*>(dv.data_ptr()), B, S, Hq,
-                     Hk, scale, causal);
+  dim3 grid1(Sp / bwd::BR, B * Hk);
+  hipLaunchKernelGGL((bwd::flash_bwd_dkv_kernel<DH, bwd::KTW1>), grid1,
+                     dim3(512 / bwd::KTW1), 0, stream.stream(), sp(q), sp(k),
+                     sp(v), sp(dout), sp(qT), sp(doT), lseP.data_ptr<float>(),
+                     drow.data_ptr<float>(), mp, spm(dk), spm(dv), B, S, Sp,
+                     Hq, Hk, scale, causal);
   HIP_CHECK_KERNEL();
-  dim3 grid2((S + 63) / 64, B * Hq);
+  dim3 grid2(Sp / bwd::BR, B * Hq);
   hipLaunchKernelGGL(bwd::flash_bwd_dq_kernel<DH>, grid2, dim3(256), 0,
-                     stream.stream(),
-                     reinterpret_cast<const short*>(q.data_ptr()),
-                     reinterpret_cast<const short*>(k.data_ptr()),
-                     reinterpret_cast<const short*>(v.data_ptr()),
-                     reinterpret_cast<const short*>(dout.data_ptr()),
-                     lse.data_ptr<float>(), drow.data_ptr<float>(), mp,
-                     reinterpret_cast<short*>(dq.data_ptr()), B, S, Hq, Hk,
-                     scale, causal);
+                     stream.stream(), sp(q), sp(k), sp(v), sp(dout), sp(kT),
+                     lseP.data_ptr<float>(), drow.data_ptr<float>(), mp,
+                     spm(dq), B, S, Sp, Hq, Hk, scale, causal);
   HIP_CHECK_KERNEL();
 }
 
