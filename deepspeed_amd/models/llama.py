@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops.attention import flash_attention
+from ..ops.attention import flash_attention, rope_flash_attention
 from ..ops.functional import (apply_rope, build_rope_cache,
                               fused_cross_entropy, rms_norm, swiglu)
 
@@ -102,6 +102,12 @@ class LlamaAttention(nn.Module):
             # pool write and the slot lengths are one kernel launch
             q, k, v = kv_cache.rope_append(q, k, v)
         else:
+            if kv_cache is None and self._dist_attn is None:
+                # plain training path: RoPE of q and k in one launch, its
+                # backward inside the flash backward epilogues
+                o = rope_flash_attention(q, k, v, cos, sin, causal=True)
+                if o is not None:
+                    return self.o_proj(o.reshape(B, S, -1))
             q = apply_rope(q, cos, sin)
             k = apply_rope(k, cos, sin)
             if kv_cache is not None:

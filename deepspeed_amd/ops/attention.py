@@ -44,69 +44,108 @@ class _FlashAttnFn(torch.autograd.Function):
         q, k, v, out, lse, kvmask = ctx.saved_tensors
         if kvmask.numel() == 0:
             kvmask = None
-        causal, scale = ctx.causal, ctx.scale
-        B, S, Hq, D = q.shape
-        Hk = k.shape[2]
-        G = Hq // Hk
+        dq, dk, dv = _flash_backward(q, k, v, out, lse, kvmask, ctx.causal,
+                                     ctx.scale, dout)
+        return dq, dk, dv, None, None, None
 
-        if os.environ.get("DSAMD_FLASH_BWD", "1") == "1":
-            ext = get_ext(required=True)
-            dq, dk, dv = ext.flash_attn_bwd(
-                q, k, v, dout.contiguous(), out, lse, causal, scale, kvmask)
-            return dq, dk, dv, None, None, None
 
-        # head-major views [B,H,S,D]
-        qh = q.permute(0, 2, 1, 3)
-        kh = k.permute(0, 2, 1, 3)
-        vh = v.permute(0, 2, 1, 3)
-        doh = dout.permute(0, 2, 1, 3).contiguous()
-        oh = out.permute(0, 2, 1, 3)
+def _flash_backward(q, k, v, out, lse, kvmask, causal, scale, dout,
+                    cos=None, sin=None):
+    """dq, dk, dv of flash attention from the saved LSE. With cos/sin, q and
+    k are the RoPE-rotated tensors and dq, dk are returned with respect to
+    the un-rotated ones: the HIP kernels un-rotate in their epilogues, the
+    reference route (DSAMD_FLASH_BWD=0) runs the rope kernel afterwards."""
+    B, S, Hq, D = q.shape
+    Hk = k.shape[2]
+    G = Hq // Hk
 
-        # D_i = rowsum(dO * O)  [B,Hq,S]
-        drow = (doh.float() * oh.float()).sum(-1)
+    if os.environ.get("DSAMD_FLASH_BWD", "1") == "1":
+        ext = get_ext(required=True)
+        dq, dk, dv = ext.flash_attn_bwd(
+            q, k, v, dout.contiguous(), out, lse, causal, scale, kvmask,
+            cos, sin)
+        return dq, dk, dv
 
-        qg = qh.reshape(B, Hk, G, S, D)
-        dog = doh.reshape(B, Hk, G, S, D)
-        lse_g = lse.reshape(B, Hk, G, S)
-        drow_g = drow.reshape(B, Hk, G, S)
+    # head-major views [B,H,S,D]
+    qh = q.permute(0, 2, 1, 3)
+    kh = k.permute(0, 2, 1, 3)
+    vh = v.permute(0, 2, 1, 3)
+    doh = dout.permute(0, 2, 1, 3).contiguous()
+    oh = out.permute(0, 2, 1, 3)
 
-        dq = torch.zeros(B, Hk, G, S, D, device=q.device, dtype=torch.float32)
-        dk = torch.empty_like(kh, dtype=torch.float32)
-        dv = torch.empty_like(vh, dtype=torch.float32)
+    # D_i = rowsum(dO * O)  [B,Hq,S]
+    drow = (doh.float() * oh.float()).sum(-1)
 
-        CHUNK = 1024
-        rows = torch.arange(S, device=q.device)
-        for c0 in range(0, S, CHUNK):
-            c1 = min(c0 + CHUNK, S)
-            kc = kh[:, :, c0:c1]          # [B,Hk,c,D]
-            vc = vh[:, :, c0:c1]
-            # S_c = q @ k^T * scale  -> P via saved LSE
-            s_c = torch.einsum("bhgsd,bhcd->bhgsc", qg, kc).float() * scale
-            if kvmask is not None:
-                s_c = s_c + kvmask[:, c0:c1].view(B, 1, 1, 1, c1 - c0)
-            p = torch.exp(s_c - lse_g.unsqueeze(-1))
-            if causal:
-                mask = rows.view(1, 1, 1, S, 1) >= (c0 + torch.arange(
-                    c1 - c0, device=q.device)).view(1, 1, 1, 1, -1)
-                p = p * mask
-            p16 = p.to(q.dtype)
-            # dV_c = P^T @ dO   (sum over G and S)
-            dv[:, :, c0:c1] = torch.einsum("bhgsc,bhgsd->bhcd", p16,
-                                           dog).float()
-            # dP = dO @ V^T
-            dp = torch.einsum("bhgsd,bhcd->bhgsc", dog, vc).float()
-            ds = (p * (dp - drow_g.unsqueeze(-1)) * scale).to(q.dtype)
-            # dQ += dS @ K
-            dq += torch.einsum("bhgsc,bhcd->bhgsd", ds, kc).float()
-            # dK_c = dS^T @ Q  (sum over G and S)
-            dk[:, :, c0:c1] = torch.einsum("bhgsc,bhgsd->bhcd", ds,
-                                           qg).float()
+    qg = qh.reshape(B, Hk, G, S, D)
+    dog = doh.reshape(B, Hk, G, S, D)
+    lse_g = lse.reshape(B, Hk, G, S)
+    drow_g = drow.reshape(B, Hk, G, S)
 
-        dq_out = dq.reshape(B, Hq, S, D).permute(0, 2, 1, 3).to(q.dtype)
-        dk_out = dk.permute(0, 2, 1, 3).to(k.dtype)
-        dv_out = dv.permute(0, 2, 1, 3).to(v.dtype)
-        return dq_out.contiguous(), dk_out.contiguous(), \
-            dv_out.contiguous(), None, None, None
+    dq = torch.zeros(B, Hk, G, S, D, device=q.device, dtype=torch.float32)
+    dk = torch.empty_like(kh, dtype=torch.float32)
+    dv = torch.empty_like(vh, dtype=torch.float32)
+
+    CHUNK = 1024
+    rows = torch.arange(S, device=q.device)
+    for c0 in range(0, S, CHUNK):
+        c1 = min(c0 + CHUNK, S)
+        kc = kh[:, :, c0:c1]          # [B,Hk,c,D]
+        vc = vh[:, :, c0:c1]
+        # S_c = q @ k^T * scale  -> P via saved LSE
+        s_c = torch.einsum("bhgsd,bhcd->bhgsc", qg, kc).float() * scale
+        if kvmask is not None:
+            s_c = s_c + kvmask[:, c0:c1].view(B, 1, 1, 1, c1 - c0)
+        p = torch.exp(s_c - lse_g.unsqueeze(-1))
+        if causal:
+            mask = rows.view(1, 1, 1, S, 1) >= (c0 + torch.arange(
+                c1 - c0, device=q.device)).view(1, 1, 1, 1, -1)
+            p = p * mask
+        p16 = p.to(q.dtype)
+        # dV_c = P^T @ dO   (sum over G and S)
+        dv[:, :, c0:c1] = torch.einsum("bhgsc,bhgsd->bhcd", p16,
+                                       dog).float()
+        # dP = dO @ V^T
+        dp = torch.einsum("bhgsd,bhcd->bhgsc", dog, vc).float()
+        ds = (p * (dp - drow_g.unsqueeze(-1)) * scale).to(q.dtype)
+        # dQ += dS @ K
+        dq += torch.einsum("bhgsc,bhcd->bhgsd", ds, kc).float()
+        # dK_c = dS^T @ Q  (sum over G and S)
+        dk[:, :, c0:c1] = torch.einsum("bhgsc,bhgsd->bhcd", ds,
+                                       qg).float()
+
+    dq_out = dq.reshape(B, Hq, S, D).permute(0, 2, 1, 3).to(q.dtype)
+    dk_out = dk.permute(0, 2, 1, 3).to(k.dtype)
+    dv_out = dv.permute(0, 2, 1, 3).to(v.dtype)
+    dq_out, dk_out = dq_out.contiguous(), dk_out.contiguous()
+    if cos is not None:
+        ext = get_ext(required=True)
+        ext.rope_inplace(dq_out, cos, sin, 0, True)
+        ext.rope_inplace(dk_out, cos, sin, 0, True)
+    return dq_out, dk_out, dv_out.contiguous()
+
+
+class _RopeFlashAttnFn(torch.autograd.Function):
+    """RoPE of q and k (one launch) + causal flash attention; backward is
+    flash backward with the inverse rotation fused into its epilogues, so
+    no standalone rope kernel runs over dq and dk."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cos, sin, causal, scale):
+        ext = get_ext(required=True)
+        qr, kr = ext.rope_qk(q.contiguous(), k.contiguous(), cos, sin)
+        v = v.contiguous()
+        out, lse = ext.flash_attn_fwd(qr, kr, v, causal, scale, None)
+        ctx.save_for_backward(qr, kr, v, out, lse, cos, sin)
+        ctx.causal = causal
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qr, kr, v, out, lse, cos, sin = ctx.saved_tensors
+        dq, dk, dv = _flash_backward(qr, kr, v, out, lse, None, ctx.causal,
+                                     ctx.scale, dout, cos, sin)
+        return dq, dk, dv, None, None, None, None
 
 
 # Training default: the in-tree HIP kernels (fwd v5 beats SDPA; bwd beats
@@ -134,6 +173,27 @@ def _as_kv_padding_mask(attn_mask, B, Sk):
     if m.shape[0] != B:
         return None
     return m.contiguous().float()
+
+
+def rope_flash_attention(q, k, v, cos, sin, causal=True):
+    """flash_attention(rope(q), rope(k), v) for the plain training path, or
+    None when that path does not apply (CPU, not bf16, per-row positions,
+    DSAMD_FLASH=0 or DSAMD_FLASH_BWD=0): the caller then takes the unfused
+    apply_rope + flash_attention route."""
+    D = q.shape[-1]
+    if not (_USE_HIP_FLASH and q.is_cuda and q.dtype == torch.bfloat16
+            and D in (64, 128) and q.shape[1] == k.shape[1]
+            and cos.dim() == 2 and cos.is_cuda
+            and cos.shape[0] >= q.shape[1] and cos.shape[1] == D // 2
+            and os.environ.get("DSAMD_FLASH_BWD", "1") == "1"):
+        return None
+    # engine-wide .to(bf16) casts buffers; the table must stay fp32
+    cos = cos.float().contiguous()
+    sin = sin.float().contiguous()
+    if cos.data_ptr() % 16 or sin.data_ptr() % 16:
+        return None
+    return _RopeFlashAttnFn.apply(q, k, v, cos, sin, causal,
+                                  1.0 / math.sqrt(D))
 
 
 def flash_attention(q, k, v, causal=True, attn_mask=None):

@@ -216,12 +216,33 @@ DEV_INLINE void store4(short* p, const f32x4_t& a) {
   *reinterpret_cast<u32x2_t*>(p) = w;
 }
 
+// Inverse RoPE (rotate-half) on one row's gradient held as NDT d-tiles of 4:
+// d = 16dt + 4*l4 .. +3 pairs with d + D/2, i.e. tile dt + NDT/2 of the same
+// lane. cr/sr point at the row's cos/sin table entries [p, 4*l4]. fp32, before
+// the single bf16 rounding in store4.
+template <int NDT, int STRIDE>
+DEV_INLINE void unrotate_row(f32x4_t* acc /* [NDT] tiles, STRIDE apart */,
+                             const float* __restrict__ cr,
+                             const float* __restrict__ sr) {
+#pragma unroll
+  for (int dt = 0; dt < NDT / 2; ++dt) {
+    const f32x4_t c = *reinterpret_cast<const f32x4_t*>(cr + 16 * dt);
+    const f32x4_t sn = *reinterpret_cast<const f32x4_t*>(sr + 16 * dt);
+    const f32x4_t d1 = acc[dt * STRIDE];
+    const f32x4_t d2 = acc[(dt + NDT / 2) * STRIDE];
+    acc[dt * STRIDE] = d1 * c + d2 * sn;
+    acc[(dt + NDT / 2) * STRIDE] = d2 * c - d1 * sn;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // PASS 1: kv-outer. Block: 8 / KTW waves x 16 * KTW keys = 128 keys; q steps
 // of 32 over every q head of the group. Accumulates dK^T, dV^T (d on the
 // register row, key on the lane).
 // ---------------------------------------------------------------------------
-template <int DH, int KTW>
+// ROPE: q and k are the rotated tensors forward attended over; dk is returned
+// with respect to the un-rotated k (rope_cos/rope_sin: fp32 [>=S, DH/2]).
+template <int DH, int KTW, bool ROPE>
 __launch_bounds__(512 / KTW, 1)
 __global__ void flash_bwd_dkv_kernel(
     const short* __restrict__ q,     // [B,S,Hq,D]
@@ -235,6 +256,8 @@ __global__ void flash_bwd_dkv_kernel(
     const float* __restrict__ kvmask,  // [B,S] or null
     short* __restrict__ dk,          // [B,S,Hk,D]
     short* __restrict__ dv,          // [B,S,Hk,D]
+    const float* __restrict__ rope_cos,  // ROPE only, else null
+    const float* __restrict__ rope_sin,
     int B, int S, int Sp, int Hq, int Hk, float scale, int causal) {
   constexpr int NKS = DH / 32;        // k-slices of the S / dP products
   constexpr int NDT = DH / 16;        // d-tiles of dK^T / dV^T
@@ -429,6 +452,10 @@ __global__ void flash_bwd_dkv_kernel(
     if (gkv >= S) continue;
     short* dkr = dk + ((long long)b * S + gkv) * kvrs + hk * DH + 4 * l4;
     short* dvr = dv + ((long long)b * S + gkv) * kvrs + hk * DH + 4 * l4;
+    if (ROPE)
+      unrotate_row<NDT, KTW>(&dk_acc[0][kt],
+                             rope_cos + (long long)gkv * (DH / 2) + 4 * l4,
+                             rope_sin + (long long)gkv * (DH / 2) + 4 * l4);
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) {
       store4(dkr + 16 * dt, dk_acc[dt][kt]);
@@ -441,7 +468,8 @@ __global__ void flash_bwd_dkv_kernel(
 // PASS 2: q-outer. Block: 4 waves x 32 q rows = 128; kv steps of 32.
 // Accumulates dQ^T (d on the register row, q on the lane).
 // ---------------------------------------------------------------------------
-template <int DH>
+// ROPE: as in pass 1; dq is returned with respect to the un-rotated q.
+template <int DH, bool ROPE>
 __launch_bounds__(256, 2)
 __global__ void flash_bwd_dq_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
@@ -451,6 +479,8 @@ __global__ void flash_bwd_dq_kernel(
     const float* __restrict__ drowP,  // [B,Hq,Sp]
     const float* __restrict__ kvmask,  // [B,S] or null
     short* __restrict__ dq,  // [B,S,Hq,D]
+    const float* __restrict__ rope_cos,  // ROPE only, else null
+    const float* __restrict__ rope_sin,
     int B, int S, int Sp, int Hq, int Hk, float scale, int causal) {
   constexpr int NKS = DH / 32;
   constexpr int NDT = DH / 16;
@@ -616,6 +646,10 @@ __global__ void flash_bwd_dq_kernel(
     const int gq = wq + 16 * qt + l15;
     if (gq >= S) continue;
     short* dqr = dq + ((long long)b * S + gq) * qrs + h * DH + 4 * l4;
+    if (ROPE)
+      unrotate_row<NDT, 2>(&dq_acc[0][qt],
+                           rope_cos + (long long)gq * (DH / 2) + 4 * l4,
+                           rope_sin + (long long)gq * (DH / 2) + 4 * l4);
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) store4(dqr + 16 * dt, dq_acc[dt][qt]);
   }
@@ -623,12 +657,13 @@ __global__ void flash_bwd_dq_kernel(
 
 }  // namespace bwd
 
-template <int DH>
+template <int DH, bool ROPE>
 static void launch_bwd(at::Tensor& q, at::Tensor& k, at::Tensor& v,
                        at::Tensor& dout, at::Tensor& out, at::Tensor& lse,
                        at::Tensor& dq, at::Tensor& dk, at::Tensor& dv,
-                       const float* mp, int B, int S, int Hq, int Hk,
-                       float scale, int causal) {
+                       const float* mp, const float* cosp, const float* sinp,
+                       int B, int S, int Hq, int Hk, float scale,
+                       int causal) {
   auto stream = c10::hip::getCurrentHIPStream();
   // scratch, fully rewritten (pad included) by the pre-pass of every call
   const int Sp = (S + bwd::BR - 1) / bwd::BR * bwd::BR;
@@ -651,17 +686,17 @@ static void launch_bwd(at::Tensor& q, at::Tensor& k, at::Tensor& v,
                      Sp, Hq, Hk);
   HIP_CHECK_KERNEL();
   dim3 grid1(Sp / bwd::BR, B * Hk);
-  hipLaunchKernelGGL((bwd::flash_bwd_dkv_kernel<DH, bwd::KTW1>), grid1,
+  hipLaunchKernelGGL((bwd::flash_bwd_dkv_kernel<DH, bwd::KTW1, ROPE>), grid1,
                      dim3(512 / bwd::KTW1), 0, stream.stream(), sp(q), sp(k),
                      sp(v), sp(dout), sp(qT), sp(doT), lseP.data_ptr<float>(),
-                     drow.data_ptr<float>(), mp, spm(dk), spm(dv), B, S, Sp,
-                     Hq, Hk, scale, causal);
+                     drow.data_ptr<float>(), mp, spm(dk), spm(dv), cosp, sinp,
+                     B, S, Sp, Hq, Hk, scale, causal);
   HIP_CHECK_KERNEL();
   dim3 grid2(Sp / bwd::BR, B * Hq);
-  hipLaunchKernelGGL(bwd::flash_bwd_dq_kernel<DH>, grid2, dim3(256), 0,
+  hipLaunchKernelGGL((bwd::flash_bwd_dq_kernel<DH, ROPE>), grid2, dim3(256), 0,
                      stream.stream(), sp(q), sp(k), sp(v), sp(dout), sp(kT),
                      lseP.data_ptr<float>(), drow.data_ptr<float>(), mp,
-                     spm(dq), B, S, Sp, Hq, Hk, scale, causal);
+                     spm(dq), cosp, sinp, B, S, Sp, Hq, Hk, scale, causal);
   HIP_CHECK_KERNEL();
 }
 
@@ -669,12 +704,17 @@ void flash_check_qkv(const at::Tensor& q, const at::Tensor& k,
                      const at::Tensor& v, const char* who);
 const float* flash_check_kvmask(const c10::optional<at::Tensor>& kvmask,
                                 const at::Tensor& q);
+void check_rope_table(const at::Tensor& cos, const at::Tensor& sin,
+                      const at::Tensor& ref, long long S, int D,
+                      const char* who);
 
 std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
                                        at::Tensor v, at::Tensor dout,
                                        at::Tensor out, at::Tensor lse,
                                        bool causal, double scale,
-                                       c10::optional<at::Tensor> kvmask) {
+                                       c10::optional<at::Tensor> kvmask,
+                                       c10::optional<at::Tensor> cos,
+                                       c10::optional<at::Tensor> sin) {
   flash_check_qkv(q, k, v, "flash_attn_bwd");
   CHECK_ARG(dout, at::kBFloat16);
   CHECK_ARG(out, at::kBFloat16);
@@ -696,11 +736,27 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
   auto dq = at::empty_like(q);
   auto dk = at::empty_like(k);
   auto dv = at::empty_like(v);
-  if (D == 128)
-    launch_bwd<128>(q, k, v, dout, out, lse, dq, dk, dv, mp, B, S, Hq, Hk,
-                    fscale, causal ? 1 : 0);
-  else
-    launch_bwd<64>(q, k, v, dout, out, lse, dq, dk, dv, mp, B, S, Hq, Hk,
-                   fscale, causal ? 1 : 0);
+  // cos/sin given: q, k are the rotated tensors and dq, dk come back with
+  // respect to the un-rotated ones (inverse RoPE in the epilogues)
+  TORCH_CHECK(cos.has_value() == sin.has_value(),
+              "flash_attn_bwd: cos and sin must be given together");
+  const bool rope = cos.has_value();
+  const float* cosp = nullptr;
+  const float* sinp = nullptr;
+  if (rope) {
+    check_rope_table(*cos, *sin, q, S, D, "flash_attn_bwd");
+    cosp = cos->data_ptr<float>();
+    sinp = sin->data_ptr<float>();
+  }
+  const int ic = causal ? 1 : 0;
+#define DSAMD_LAUNCH_BWD(DH_, ROPE_)                                        \
+  launch_bwd<DH_, ROPE_>(q, k, v, dout, out, lse, dq, dk, dv, mp, cosp, sinp, \
+                         B, S, Hq, Hk, fscale, ic)
+  if (D == 128) {
+    if (rope) DSAMD_LAUNCH_BWD(128, true); else DSAMD_LAUNCH_BWD(128, false);
+  } else {
+    if (rope) DSAMD_LAUNCH_BWD(64, true); else DSAMD_LAUNCH_BWD(64, false);
+  }
+#undef DSAMD_LAUNCH_BWD
   return {dq, dk, dv};
 }

@@ -9,7 +9,8 @@ void multi_tensor_adam(std::vector<at::Tensor> params,
                        long adamw_mode, long bias_correction,
                        double weight_decay, std::vector<at::Tensor> out16,
                        double grad_scale);
-void accum_bf16_to_f32(at::Tensor dst, at::Tensor src, double scale);
+void accum_bf16_to_f32(at::Tensor dst, at::Tensor src, double scale,
+                       bool overwrite);
 at::Tensor l2norm_sq(std::vector<at::Tensor> tensors);
 at::Tensor fp8_amax(at::Tensor x);
 at::Tensor ragged_decode(at::Tensor q, at::Tensor kpool, at::Tensor vpool,
@@ -45,7 +46,9 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
                                        at::Tensor v, at::Tensor dout,
                                        at::Tensor out, at::Tensor lse,
                                        bool causal, double scale,
-                                       c10::optional<at::Tensor> kvmask);
+                                       c10::optional<at::Tensor> kvmask,
+                                       c10::optional<at::Tensor> cos,
+                                       c10::optional<at::Tensor> sin);
 void multi_tensor_adagrad(std::vector<at::Tensor> params,
                           std::vector<at::Tensor> grads,
                           std::vector<at::Tensor> sq_accums, double lr,
@@ -87,6 +90,8 @@ void rope(at::Tensor dst, at::Tensor src, at::Tensor cos, at::Tensor sin,
           long pos0, bool backward);
 void rope_inplace(at::Tensor t, at::Tensor cos, at::Tensor sin, long pos0,
                   bool backward);
+std::vector<at::Tensor> rope_qk(at::Tensor q, at::Tensor k, at::Tensor cos,
+                                at::Tensor sin);
 at::Tensor swiglu_fwd(at::Tensor g, at::Tensor u);
 std::vector<at::Tensor> swiglu_bwd(at::Tensor dy, at::Tensor g, at::Tensor u);
 std::vector<at::Tensor> cross_entropy_fwd(at::Tensor logits,
@@ -121,7 +126,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("weight_decay"), py::arg("out16") = std::vector<at::Tensor>(),
         py::arg("grad_scale") = 1.0);
   m.def("accum_bf16_to_f32", &accum_bf16_to_f32, py::arg("dst"),
-        py::arg("src"), py::arg("scale") = 1.0);
+        py::arg("src"), py::arg("scale") = 1.0,
+        py::arg("overwrite") = false);
   m.def("l2norm_sq", &l2norm_sq);
   m.def("fp8_amax", &fp8_amax);
   m.def("ragged_decode", &ragged_decode, py::arg("q"), py::arg("kpool"),
@@ -175,7 +181,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_bwd", &flash_attn_bwd, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("dout"), py::arg("out"), py::arg("lse"),
         py::arg("causal") = true, py::arg("scale") = 0.0,
-        py::arg("kvmask") = c10::nullopt);
+        py::arg("kvmask") = c10::nullopt, py::arg("cos") = c10::nullopt,
+        py::arg("sin") = c10::nullopt);
   m.def("multi_tensor_adagrad", &multi_tensor_adagrad, py::arg("params"),
         py::arg("grads"), py::arg("sq_accums"), py::arg("lr"),
         py::arg("eps") = 1e-8, py::arg("weight_decay") = 0.0,
@@ -212,6 +219,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_bwd", &layernorm_bwd);
   m.def("rope", &rope);
   m.def("rope_inplace", &rope_inplace);
+  m.def("rope_qk", &rope_qk);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("cross_entropy_fwd", &cross_entropy_fwd);

@@ -14,6 +14,31 @@
 // vectorized: each lane rotates 8 consecutive pairs (bf16x8 loads from both
 // halves, float4x2 table loads) — scalar version measured 2.5 TB/s, this
 // pattern is the guide-G13 8-16 B/lane sweet spot.
+// one lane's share: 8 consecutive (d, d + D/2) pairs at element offset base
+DEV_INLINE void rope_vec8(short* __restrict__ dst,
+                          const short* __restrict__ src, long long base,
+                          int half, const float* __restrict__ crow,
+                          const float* __restrict__ srow, float sgn) {
+  bf16x8 x1 = *reinterpret_cast<const bf16x8*>(src + base);
+  bf16x8 x2 = *reinterpret_cast<const bf16x8*>(src + base + half);
+  f32x4 c0 = *reinterpret_cast<const f32x4*>(crow);
+  f32x4 c1 = *reinterpret_cast<const f32x4*>(crow + 4);
+  f32x4 s0 = *reinterpret_cast<const f32x4*>(srow);
+  f32x4 s1 = *reinterpret_cast<const f32x4*>(srow + 4);
+  bf16x8 o1, o2;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    float c = (k < 4 ? c0.v[k] : c1.v[k - 4]);
+    float sv = (k < 4 ? s0.v[k] : s1.v[k - 4]) * sgn;
+    float a = bf2f(x1.v[k]);
+    float bb = bf2f(x2.v[k]);
+    o1.v[k] = f2bf(a * c - bb * sv);
+    o2.v[k] = f2bf(bb * c + a * sv);
+  }
+  *reinterpret_cast<bf16x8*>(dst + base) = o1;
+  *reinterpret_cast<bf16x8*>(dst + base + half) = o2;
+}
+
 __global__ void rope_kernel(short* __restrict__ dst,
                             const short* __restrict__ src,
                             const float* __restrict__ cs,  // [S, D/2] cos
@@ -32,27 +57,41 @@ __global__ void rope_kernel(short* __restrict__ dst,
     int s = (int)(rem2 % S);
     long long b = rem2 / S;
     long long base = ((b * S + s) * (long long)H + h) * D + d8 * 8;
-    const float* crow = cs + (long long)(s + pos0) * half + d8 * 8;
-    const float* srow = sn + (long long)(s + pos0) * half + d8 * 8;
-    bf16x8 x1 = *reinterpret_cast<const bf16x8*>(src + base);
-    bf16x8 x2 = *reinterpret_cast<const bf16x8*>(src + base + half);
-    f32x4 c0 = *reinterpret_cast<const f32x4*>(crow);
-    f32x4 c1 = *reinterpret_cast<const f32x4*>(crow + 4);
-    f32x4 s0 = *reinterpret_cast<const f32x4*>(srow);
-    f32x4 s1 = *reinterpret_cast<const f32x4*>(srow + 4);
-    float sgn = backward ? -1.f : 1.f;
-    bf16x8 o1, o2;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      float c = (k < 4 ? c0.v[k] : c1.v[k - 4]);
-      float sv = (k < 4 ? s0.v[k] : s1.v[k - 4]) * sgn;
-      float a = bf2f(x1.v[k]);
-      float bb = bf2f(x2.v[k]);
-      o1.v[k] = f2bf(a * c - bb * sv);
-      o2.v[k] = f2bf(bb * c + a * sv);
-    }
-    *reinterpret_cast<bf16x8*>(dst + base) = o1;
-    *reinterpret_cast<bf16x8*>(dst + base + half) = o2;
+    rope_vec8(dst, src, base, half,
+              cs + (long long)(s + pos0) * half + d8 * 8,
+              sn + (long long)(s + pos0) * half + d8 * 8,
+              backward ? -1.f : 1.f);
+  }
+}
+
+// q and k in one launch: the grid runs over the Hq + Hk heads of a token;
+// heads below Hq are q's, the rest k's. Same per-element math as rope_kernel.
+__global__ void rope_qk_kernel(short* __restrict__ qd,
+                               const short* __restrict__ qs,
+                               short* __restrict__ kd,
+                               const short* __restrict__ ks,
+                               const float* __restrict__ cs,
+                               const float* __restrict__ sn,
+                               long long total_vec, int S, int Hq, int Hk,
+                               int D) {
+  int half = D / 2;
+  int half8 = half / 8;
+  int HT = Hq + Hk;
+  long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = i0; i < total_vec; i += stride) {
+    int d8 = (int)(i % half8);
+    long long rem = i / half8;
+    int h = (int)(rem % HT);
+    long long tok = rem / HT;  // b * S + s
+    int s = (int)(tok % S);
+    const float* crow = cs + (long long)s * half + d8 * 8;
+    const float* srow = sn + (long long)s * half + d8 * 8;
+    if (h < Hq)
+      rope_vec8(qd, qs, (tok * Hq + h) * D + d8 * 8, half, crow, srow, 1.f);
+    else
+      rope_vec8(kd, ks, (tok * Hk + (h - Hq)) * D + d8 * 8, half, crow, srow,
+                1.f);
   }
 }
 
@@ -131,6 +170,60 @@ void rope(at::Tensor dst, at::Tensor src, at::Tensor cos, at::Tensor sin,
                        total_pairs, S, H, D, (int)pos0, backward ? 1 : 0);
   }
   HIP_CHECK_KERNEL();
+}
+
+// Table contract shared by rope_qk and the flash backward epilogues: fp32,
+// contiguous, on ref's device, at least [S, D/2], 16-byte aligned.
+void check_rope_table(const at::Tensor& cos, const at::Tensor& sin,
+                      const at::Tensor& ref, long long S, int D,
+                      const char* who) {
+  TORCH_CHECK(cos.defined() && sin.defined() &&
+                  cos.device() == ref.device() && sin.device() == ref.device(),
+              who, ": cos/sin must be on the same device as q");
+  TORCH_CHECK(cos.scalar_type() == at::kFloat && cos.is_contiguous() &&
+                  sin.scalar_type() == at::kFloat && sin.is_contiguous(),
+              who, ": cos/sin must be contiguous fp32");
+  TORCH_CHECK(S * (D / 2) <= cos.numel() && S * (D / 2) <= sin.numel(),
+              who, ": cos/sin table shorter than [S, D/2]");
+  TORCH_CHECK(ptr_aligned(cos.data_ptr(), 16) &&
+                  ptr_aligned(sin.data_ptr(), 16),
+              who, ": cos/sin must be 16-byte aligned");
+}
+
+// Forward rotation of q [B,S,Hq,D] and k [B,S,Hk,D] in one launch (training
+// path: positions 0..S-1, vector layout required; other callers use rope()).
+std::vector<at::Tensor> rope_qk(at::Tensor q, at::Tensor k, at::Tensor cos,
+                                at::Tensor sin) {
+  CHECK_ARG(q, at::kBFloat16);
+  CHECK_ARG(k, at::kBFloat16);
+  CHECK_ON(k, q);
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && q.size(0) == k.size(0) &&
+                  q.size(1) == k.size(1) && q.size(3) == k.size(3),
+              "rope_qk expects q [B,S,Hq,D] and k [B,S,Hk,D]");
+  int B = q.size(0), S = q.size(1), Hq = q.size(2), D = q.size(3);
+  int Hk = k.size(2);
+  TORCH_CHECK(D % 16 == 0, "rope_qk: D must be a multiple of 16");
+  auto qo = at::empty_like(q);
+  auto ko = at::empty_like(k);
+  if (q.numel() + k.numel() == 0) return {qo, ko};
+  check_rope_table(cos, sin, q, S, D, "rope_qk");
+  TORCH_CHECK(ptr_aligned(q.data_ptr(), 16) && ptr_aligned(k.data_ptr(), 16) &&
+                  ptr_aligned(qo.data_ptr(), 16) &&
+                  ptr_aligned(ko.data_ptr(), 16),
+              "rope_qk: q/k must be 16-byte aligned");
+  auto stream = c10::hip::getCurrentHIPStream();
+  int block = 256;
+  long long total_vec = (long long)B * S * (Hq + Hk) * (D / 16);
+  int grid = grid_for(total_vec, block);
+  hipLaunchKernelGGL(rope_qk_kernel, dim3(grid), dim3(block), 0,
+                     stream.stream(), reinterpret_cast<short*>(qo.data_ptr()),
+                     reinterpret_cast<const short*>(q.data_ptr()),
+                     reinterpret_cast<short*>(ko.data_ptr()),
+                     reinterpret_cast<const short*>(k.data_ptr()),
+                     cos.data_ptr<float>(), sin.data_ptr<float>(), total_vec,
+                     S, Hq, Hk, D);
+  HIP_CHECK_KERNEL();
+  return {qo, ko};
 }
 
 void rope_inplace(at::Tensor t, at::Tensor cos, at::Tensor sin, long pos0,

@@ -8,6 +8,9 @@
 
 #include "common.h"
 
+// OVERWRITE: dst = float(src) * scale and dst is never read (the first
+// accumulate of a window needs no zero fill before it); else dst += ...
+template <bool OVERWRITE>
 __global__ void accum_bf16_f32_kernel(float* __restrict__ dst,
                                       const short* __restrict__ src,
                                       long long n, float scale,
@@ -19,16 +22,27 @@ __global__ void accum_bf16_f32_kernel(float* __restrict__ dst,
   for (long long i = i0; i < n4; i += stride) {
     uint2 sv = reinterpret_cast<const uint2*>(src)[i];
     const short* s = reinterpret_cast<const short*>(&sv);
-    f32x4 d = reinterpret_cast<f32x4*>(dst)[i];
+    f32x4 d;
+    if (OVERWRITE) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) d.v[k] += bf2f(s[k]) * scale;
+      for (int k = 0; k < 4; ++k) d.v[k] = bf2f(s[k]) * scale;
+    } else {
+      d = reinterpret_cast<f32x4*>(dst)[i];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) d.v[k] += bf2f(s[k]) * scale;
+    }
     reinterpret_cast<f32x4*>(dst)[i] = d;
   }
-  for (long long i = n4 * 4 + i0; i < n; i += stride)
-    dst[i] += bf2f(src[i]) * scale;
+  for (long long i = n4 * 4 + i0; i < n; i += stride) {
+    if (OVERWRITE)
+      dst[i] = bf2f(src[i]) * scale;
+    else
+      dst[i] += bf2f(src[i]) * scale;
+  }
 }
 
-void accum_bf16_to_f32(at::Tensor dst, at::Tensor src, double scale) {
+void accum_bf16_to_f32(at::Tensor dst, at::Tensor src, double scale,
+                       bool overwrite) {
   CHECK_ARG(dst, at::kFloat);
   CHECK_ARG(src, at::kBFloat16);
   CHECK_LIKE(src, dst);
@@ -38,8 +52,10 @@ void accum_bf16_to_f32(at::Tensor dst, at::Tensor src, double scale) {
   auto stream = c10::hip::getCurrentHIPStream();
   int block = 256;
   int grid = grid_for(n / 4 + 1, block);
-  hipLaunchKernelGGL(accum_bf16_f32_kernel, dim3(grid), dim3(block), 0,
-                     stream.stream(), dst.data_ptr<float>(),
+  auto kern = overwrite ? accum_bf16_f32_kernel<true>
+                        : accum_bf16_f32_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, stream.stream(),
+                     dst.data_ptr<float>(),
                      reinterpret_cast<const short*>(src.data_ptr()), n,
                      (float)scale, vec_ok);
   HIP_CHECK_KERNEL();

@@ -289,6 +289,7 @@ class ZenFlowZeroStage3Optimizer(ZeroStage3Optimizer):
         self._flush_ipg()
         self._sync_comm_streams()
         self._drain_inflight()
+        self._complete_grads()
         self._cached_norm_sq = None
         if self.dtype == torch.float16:
             self.overflow = self.has_overflow()

@@ -41,7 +41,8 @@ class SubGroup:
 
     __slots__ = ("params", "offsets", "master32", "grad32", "flat16",
                  "flat16_cpu", "grad_stage", "group_idx", "numel", "offload",
-                 "param_offload", "dtype16")
+                 "param_offload", "dtype16", "store_first", "_written",
+                 "_stale")
 
     def __init__(self, params, offsets, numel, group_idx, device,
                  offload=False, param_offload=False, pin_opt=True,
@@ -94,6 +95,19 @@ class SubGroup:
         else:
             self.flat16_cpu = None
             self.grad_stage = None
+        # Store-first accumulation (device-resident grads only): instead of
+        # zero-filling grad32 after every step and adding onto the zeros,
+        # the first accumulate of a parameter in a window overwrites its
+        # range. `_written`: ranges valid in this window. `_stale`: ranges
+        # still holding the previous window's data; `complete_grads` zeroes
+        # the ones the window never wrote before anything reads grad32.
+        # The offsets tile [0, numel) with whole-parameter ranges, so there
+        # is no padding between ranges; within a range, elements past the
+        # reduced shard's length are never written and keep the zero from
+        # the allocation above.
+        self.store_first = not offload
+        self._written = set()
+        self._stale = set()
 
     def grad_shard_view(self, p):
         off = self.offsets[p]
@@ -109,11 +123,34 @@ class SubGroup:
             if shard16_gpu.is_cuda:
                 torch.cuda.synchronize()
             dst.add_(stage.float())
-        elif shard16_gpu.is_cuda and shard16_gpu.dtype == torch.bfloat16:
+            return
+        overwrite = self.store_first and p not in self._written
+        self._written.add(p)
+        if shard16_gpu.is_cuda and shard16_gpu.dtype == torch.bfloat16:
             from ...ops.loader import get_ext
-            get_ext(required=True).accum_bf16_to_f32(dst, shard16_gpu, 1.0)
+            get_ext(required=True).accum_bf16_to_f32(dst, shard16_gpu, 1.0,
+                                                     overwrite)
+        elif overwrite:
+            dst.copy_(shard16_gpu)
         else:
             dst.add_(shard16_gpu.float())
+
+    def complete_grads(self):
+        """Make every range of grad32 valid for a reader: zero the ranges
+        that hold the previous window's data and were not written since."""
+        for p in self._stale:
+            if p not in self._written:
+                self.grad_shard_view(p).zero_()
+        self._stale.clear()
+
+    def clear_grads(self):
+        """Start a new accumulation window."""
+        if self.store_first:
+            self._stale |= self._written
+        else:
+            self.grad32.zero_()
+            self._stale.clear()
+        self._written.clear()
 
     def copy_master_to_shards(self):
         if self.offload:
@@ -1043,6 +1080,7 @@ class ZeroStage3Optimizer:
         all-reduced over DP. Serves BOTH the overflow check (inf/nan in any
         grad makes the squared sum non-finite) and grad clipping — the
         separate grad32.sum() scan the fp16 path used to do is folded in."""
+        self._complete_grads()
         grads = [sg.grad32 for sg in self.sub_groups]
         if grads and grads[0].is_cuda:
             from ...ops.loader import get_ext
@@ -1102,6 +1140,7 @@ class ZeroStage3Optimizer:
         self._flush_ipg()
         self._sync_comm_streams()
         self._drain_inflight()
+        self._complete_grads()
         self._cached_norm_sq = None  # one norm pass per step, shared below
 
         if self.dtype == torch.float16:
@@ -1177,8 +1216,22 @@ class ZeroStage3Optimizer:
             self._gather_grouped(persist, async_op=False).wait()
 
     def _clear_grads(self):
+        # device-resident sub-groups start a store-first window (no fill);
+        # host-resident ones are zero-filled as before
         for sg in self.sub_groups:
-            sg.grad32.zero_()
+            sg.clear_grads()
+
+    def _set_store_first(self, enabled):
+        """Private switch (tests): False restores fill-then-add."""
+        self._complete_grads()
+        for sg in self.sub_groups:
+            sg.store_first = bool(enabled) and not sg.offload
+
+    def _complete_grads(self):
+        """Call before anything reads grad32: ranges no accumulate wrote
+        in this window read as zero, never as the previous window's data."""
+        for sg in self.sub_groups:
+            sg.complete_grads()
 
     def zero_grad(self, set_to_none=True):
         pass

@@ -138,6 +138,9 @@ def safe_get_full_grad(param, optimizer=None):
     if kind == "subgroup":
         pg = opt.dp_group
         world = dist.get_world_size(pg)
+        # store-first accumulation: ranges not written in this window
+        # must read as zero, not as the previous window's gradient
+        container.complete_grads()
         shard = container.grad32.detach().float()[off:off + shard_numel]
         if world == 1:
             return shard[:param.ds_numel].reshape(param.ds_shape)
