@@ -32,8 +32,11 @@ DEV_INLINE void rope_vec8(short* __restrict__ dst,
     float sv = (k < 4 ? s0.v[k] : s1.v[k - 4]) * sgn;
     float a = bf2f(x1.v[k]);
     float bb = bf2f(x2.v[k]);
-    o1.v[k] = f2bf(a * c - bb * sv);
-    o2.v[k] = f2bf(bb * c + a * sv);
+    // the fused multiply-adds are spelled out: left to the compiler, the
+    // contraction differed between rope_kernel and rope_qk_kernel (one
+    // element per lane got mul, mul, sub), and with it the rounded bits
+    o1.v[k] = f2bf(__builtin_fmaf(a, c, -(bb * sv)));
+    o2.v[k] = f2bf(__builtin_fmaf(bb, c, a * sv));
   }
   *reinterpret_cast<bf16x8*>(dst + base) = o1;
   *reinterpret_cast<bf16x8*>(dst + base + half) = o2;

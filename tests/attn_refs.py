@@ -46,6 +46,29 @@ ragged fp32 throughout: with L keys, eta as above (S -> L, no +8) and
        4 * (L + D + EPI) * U24 for the accumulation (L), the chain of at most
        L online rescales (a multiply and an exp, 3 units each) and the
        split-KV combine -- all times P @ |V|, plus the final bf16 rounding.
+
+Un-rotated dQ / dK (flash backward given cos / sin tables)
+----------------------------------------------------------
+q and k are then the RoPE-rotated tensors, and the epilogues return the
+gradient with respect to the un-rotated ones: the inverse rotate-half
+rotation at table row s, applied to the fp32 accumulators BEFORE their single
+bf16 rounding. With (d1, d2) the exact gradient pair at columns (j, j + D/2),
+c = cos[s, j] and s = sin[s, j] (the fp32 table values, taken to float64
+exactly: kernel and reference read the same table), the reference is
+         d1' = d1 c + d2 s,     d2' = d2 c - d1 s.
+The kernel holds d1, d2 off by at most e1, e2 (dq_slack / dk_slack above: the
+pre-rounding slack of dQ / dK) and forms both expressions in fp32: two
+products and one sum, 3 roundings of at most U24 each relative to
+|c||d1| + |s||d2| (a fused multiply-add only drops one of them). So before the
+final rounding
+         slack1' = |c| e1 + |s| e2 + 3 U24 (|c||d1| + |s||d2|)
+         slack2' = |c| e2 + |s| e1 + 3 U24 (|c||d2| + |s||d1|)
+and tol' = bf16_tol(ref', slack'). Nothing here is tuned. The unfused route
+(bf16 dQ, then the rope kernel: two roundings) is NOT a mutant of this bound:
+its extra rounding (2^-8 |d1|, 2^-8 |d2| before the rotation) is of the order
+of the allowance 2^-7 |ref'| for the final one, and the emulated unfused
+route lies inside on every shared case (test_flash_bwd_rope_refs_cpu.py
+checks that too), so no test asserts that it falls outside.
 """
 import math
 
@@ -68,7 +91,8 @@ def attention_ref(q, k, v, causal, scale, kvmask=None, dout=None):
     """All float64, closed form. q [B,S,Hq,D], k/v [B,S,Hk,D], kvmask [B,S]
     additive or None, dout [B,S,Hq,D] or None. Returns a dict of references
     in the kernels' layouts (out/dq [B,S,Hq,D], dk/dv [B,S,Hk,D],
-    lse [B,Hq,S]), the condition terms and the tolerances derived above."""
+    lse [B,Hq,S]), the condition terms and the tolerances derived above;
+    dq_slack / dk_slack are the pre-rounding parts of dq_tol / dk_tol."""
     B, S, Hq, D = q.shape
     Hk = k.shape[2]
     G = Hq // Hk
@@ -146,11 +170,57 @@ def attention_ref(q, k, v, causal, scale, kvmask=None, dout=None):
     dk = group(ds.transpose(-1, -2) @ qd)
     dv = group(p.transpose(-1, -2) @ do)
     dq = dq.permute(0, 2, 1, 3)
+    dq_slack = dq_slack.permute(0, 2, 1, 3)
     r.update(dq=dq, dk=dk, dv=dv, do_o_abs=do_o_abs, dq_terms=dq_terms,
              pt_do_abs=pt_do_abs, dst_q_abs=dst_q_abs,
-             dq_tol=bf16_tol(dq, dq_slack.permute(0, 2, 1, 3)),
+             dq_slack=dq_slack, dk_slack=dk_slack,
+             dq_tol=bf16_tol(dq, dq_slack),
              dk_tol=bf16_tol(dk, dk_slack), dv_tol=bf16_tol(dv, dv_slack))
     return r
+
+
+def unrotate_ref(d, slack, cos, sin):
+    """Inverse rotate-half rotation at table row s of a float64 gradient
+    d [B,S,H,D] that the kernel holds to within `slack` before rounding.
+    cos / sin: fp32 [>= S, D/2], rows 0..S-1 used. Returns (reference,
+    elementwise tolerance), derived in the module docstring."""
+    S, D = d.shape[1], d.shape[3]
+    half = D // 2
+    c = cos[:S].to(d.device).double().reshape(1, S, 1, half)
+    s = sin[:S].to(d.device).double().reshape(1, S, 1, half)
+    d1, d2 = d[..., :half], d[..., half:]
+    e1, e2 = slack[..., :half], slack[..., half:]
+    ca, sa = c.abs(), s.abs()
+    ref = torch.cat([d1 * c + d2 * s, d2 * c - d1 * s], -1)
+    sl = torch.cat([ca * e1 + sa * e2 + 3.0 * U24 * (ca * d1.abs() +
+                                                      sa * d2.abs()),
+                    ca * e2 + sa * e1 + 3.0 * U24 * (ca * d2.abs() +
+                                                      sa * d1.abs())], -1)
+    return ref, bf16_tol(ref, sl)
+
+
+def unrotated_grads(r, cos, sin):
+    """dq, dk of attention_ref's dict `r` with respect to the un-rotated q and
+    k, and their tolerances."""
+    dq, dq_tol = unrotate_ref(r["dq"], r["dq_slack"], cos, sin)
+    dk, dk_tol = unrotate_ref(r["dk"], r["dk_slack"], cos, sin)
+    return dict(dq=dq, dq_tol=dq_tol, dk=dk, dk_tol=dk_tol)
+
+
+def make_rope_tables(S, D, extra=3, device="cpu", seed=0, poison=True):
+    """cos, sin [S + extra, D/2], fp32, contiguous: one angle per (row,
+    column), uniform in [0, 2 pi), so every entry is distinct and of order 1
+    and a wrong row, column or sign shows in every column. The kernels only
+    read the table, so it need not be a RoPE table. poison: rows S.. are NaN
+    (no kernel may read them); otherwise they hold angles like the rest."""
+    g = torch.Generator().manual_seed(seed + 104729 * S + D)
+    ang = torch.rand(S + extra, D // 2, generator=g,
+                     dtype=torch.float64) * (2.0 * math.pi)
+    cos, sin = ang.cos().float(), ang.sin().float()
+    if poison:
+        cos[S:] = float("nan")
+        sin[S:] = float("nan")
+    return cos.contiguous().to(device), sin.contiguous().to(device)
 
 
 def check_attention(got, r, what, backward=True):
@@ -264,8 +334,10 @@ def _c(S, D, H, causal, custom=False, mask=None, arg=None):
                 mask=mask, arg=arg)
 
 
-# Tile sizes straddled: forward 256 rows/block, 32/wave, 64 kv/tile;
-# backward 64-kv blocks, 32-q steps, 64-q dq tiles.
+# Tile sizes straddled: forward 256 rows/block, 32/wave, 64 kv/tile. The
+# backward (128-row workgroups of 4 waves x 32 rows in both passes, 32-row
+# streamed steps, scratch padded to 128 and written in 64-row tiles) has its
+# own cases in attn_bwd_tile_cases.py.
 ATTN_CASES = [
     # unmasked: every S, causal and not, both D, every head layout
     _c(1, 64, (1, 1), True), _c(1, 128, (4, 1), False, True),

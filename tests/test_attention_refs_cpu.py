@@ -20,11 +20,13 @@ def _r16(t):              # round to bf16, keep computing in fp32
     return t.to(BF).float()
 
 
-def emulate_attention(q, k, v, causal, scale, kvmask, dout, mut=None):
+def emulate_attention(q, k, v, causal, scale, kvmask, dout, mut=None,
+                      fp32_grads=False):
     """What the kernels do, in plain torch: bf16 inputs, fp32 scores, P and
     dS rounded to bf16 before their matmuls, fp32 accumulation, Drow from the
     bf16 O, P recomputed from the saved fp32 lse, bf16 outputs. `mut` names
-    one deliberately broken edge."""
+    one deliberately broken edge. fp32_grads: also return dq32 / dk32, the
+    fp32 accumulators of dq / dk before their final rounding."""
     B, S, Hq, D = q.shape
     Hk = k.shape[2]
     G = Hq // Hk
@@ -76,7 +78,8 @@ def emulate_attention(q, k, v, causal, scale, kvmask, dout, mut=None):
     drow = (do * out.float()).sum(-1)
     dp = do @ vf.transpose(-1, -2)
     ds = pb * (dp - drow.unsqueeze(-1)) * scale
-    dq = (_r16(ds) @ kf).to(BF)
+    dq32 = _r16(ds) @ kf
+    dq = dq32.to(BF)
     dk_h = _r16(ds).transpose(-1, -2) @ qf                  # [B,Hq,S,D]
     dv_h = _r16(pb).transpose(-1, -2) @ do
     dk = torch.zeros(B, Hk, S, D)
@@ -90,8 +93,11 @@ def emulate_attention(q, k, v, causal, scale, kvmask, dout, mut=None):
         dk[:, hk] += dk_h[:, h]
         dv[:, hk] += dv_h[:, h]
     perm = lambda t: t.permute(0, 2, 1, 3)                  # noqa: E731
-    return dict(out=perm(out), lse=lse, dq=perm(dq), dk=perm(dk).to(BF),
-                dv=perm(dv).to(BF))
+    got = dict(out=perm(out), lse=lse, dq=perm(dq), dk=perm(dk).to(BF),
+               dv=perm(dv).to(BF))
+    if fp32_grads:
+        got.update(dq32=perm(dq32), dk32=perm(dk))
+    return got
 
 
 # mutant -> which cases have the edge at all

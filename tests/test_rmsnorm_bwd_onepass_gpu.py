@@ -100,6 +100,27 @@ def test_register_limit_and_two_kernel_path(rows, H):
     _check(rows, H)
 
 
+@pytest.mark.parametrize("rows,H", [(4097, 250), (4097, 8200)])
+def test_two_kernel_path_with_64_partial_rows(rows, H):
+    # rows > 4096 on the two-kernel path (scalar row / past the register
+    # limit): dw partials strided over 64 grid rows
+    assert rows > 4096 and (H % 8 or H > 8192)
+    _check(rows, H)
+
+
+@pytest.mark.parametrize("rows,H", [(3073, 64), (3073, 4104)])
+def test_onepass_chunks_longer_than_two_rows(rows, H):
+    """One-pass kernel (NV = 1 and 4) on chunks of three rows or more, so a
+    steady-state row has both a predecessor and a successor in its chunk
+    (`more` true on entry and on exit), and a short last chunk."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    per = -(-rows // (4 * cus))             # rmsnorm_bwd: 4 workgroups per CU
+    assert per >= 3, f"{cus} CUs give chunks of {per} rows: arm not reached"
+    assert rows % per, "the last chunk must be shorter than the others"
+    assert H % 8 == 0 and H <= 8192
+    _check(rows, H)
+
+
 @pytest.mark.parametrize("rows,H", [(3, 72), (1031, 72)])
 def test_unaligned_bases_take_scalar_path(rows, H):
     # a sliced input whose base sits 2 bytes past 16-byte alignment
