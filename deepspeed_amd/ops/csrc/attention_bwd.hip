@@ -5,12 +5,11 @@
 //   pass 2 (q-outer):  dQ = dS K                     — no atomics
 // with dS = P o (dP - Drow) * scale, dP = dO V^T, P = exp(S*scale - lse).
 //
-// Pre-pass (bwd_preprocess, once per call): writes the transposed images
-// Q^T, dO^T [B,Hq,D,Sp] and K^T [B,Hk,D,Sp], Drow = rowsum(dO o O) and a
+// Pre-pass (bwd_preprocess, once per call): Drow = rowsum(dO o O) and a
 // copy of lse (with -inf -> +inf, so exp(s - lse) = 0 on rows that have no
 // admissible column), both [B,Hq,Sp]. Sp is S padded to a multiple of 128 and
-// the pad is written as zeros, so every tile read of the scratch is in
-// bounds and no tile loop stores a transposed element itself.
+// the pad is written as zeros, so every read of them is in bounds. They are
+// the only scratch: no transposed copy of Q, dO or K exists.
 //
 // Both passes have the same shape: a workgroup owns 128 rows of its outer
 // index (pass 1: 8 waves x 16 keys; pass 2: 4 waves x 32 q rows) and streams
@@ -21,12 +20,16 @@
 //     16x16 accumulator tiles, rounded to bf16, is then already the B operand
 //     of the second products (dV^T += dO^T P, dK^T += Q^T dS; dQ^T += K^T
 //     dS^T): P and dS never cross LDS. The A operand of those products comes
-//     from the transposed image with the matching k order (element j of lane
-//     group l4 is row 4*l4 + j for j < 4 and 16 + 4*l4 + j - 4 above), two
-//     8-byte LDS reads.
-//   - each step's images (row-major + transposed, and in pass 1 the step's
-//     lse / Drow) arrive by global_load_lds into a double buffer; step t+1
-//     is issued before step t's MFMAs, one barrier per step.
+//     from the SAME row-major image as the first products' (Q, dO; K), read
+//     transposed in hardware with the matching k order (element j of lane
+//     group l4 is row 4*l4 + j for j < 4 and 16 + 4*l4 + j - 4 above): two
+//     ds_read_b64_tr_b16, issued one d-tile ahead of their MFMAs.
+//   - each step's images (pass 1: Q, dO and the step's lse / Drow; pass 2:
+//     K, V), one per tile, arrive by global_load_lds into a double buffer;
+//     step t+1 is issued before step t's MFMAs, one barrier per step. Rows
+//     past S-1 of an image repeat row S-1; the predicate zeroes their P, dS.
+//     (A three-deep ring with counted vmcnt waits was measured slower in
+//     pass 1: profiles/README.md.)
 //   - -Drow is the initial accumulator of dP.
 //   - steps with nothing to mask (all rows in range, below the causal
 //     diagonal, no kv mask) skip the predicate; steps fully above the
@@ -37,15 +40,15 @@
 //
 // Layout conventions follow the forward kernel (attention.hip): C/D layout
 // row=(lane>>4)*4+reg, col=lane&15; A-operand lane holds A[l15][l4*8+j];
-// row-major LDS tiles use the ((row&7)<<4) XOR swizzle with pre-swizzled
-// sources; transposed tiles are [D][32] with the 16-byte granule XORed by
-// (d>>2)&3.
+// the LDS image layout (32-byte pair XOR, conflict-free for both kinds of
+// read, pre-swizzled DMA sources) is in flash_bwd_layout.h.
 // GQA: pass 1 accumulates over the q-head group in-kernel (K/V fragments
 // stay in registers across the group), writing dK/dV at [B,S,Hk,D]
 // directly — no per-q-head buffers, no wrapper reduction.
 #include <torch/extension.h>
 
 #include "common.h"
+#include "flash_bwd_layout.h"
 
 using bf16x8_t = __attribute__((ext_vector_type(8))) short;
 using f32x4_t = __attribute__((ext_vector_type(4))) float;
@@ -63,6 +66,7 @@ constexpr int WR = 32;    // q rows per wave, pass 2 (4 waves)
 // 256-register budget and was slower at one wave per SIMD than 1 at two.
 constexpr int KTW1 = 1;
 constexpr int TS = 32;    // streamed rows per step
+static_assert(TS == bwd_layout::TS, "the image layout is for 32-row steps");
 constexpr int PT = 64;    // rows per pre-pass tile
 
 // two f32 -> one u32 of 2 bf16, RNE (v_cvt_pk_bf16_f32)
@@ -73,52 +77,42 @@ DEV_INLINE unsigned int cvtpk2(float lo, float hi) {
 }
 
 // ---------------------------------------------------------------------------
-// PRE-PASS. grid (Sp/64, B*Hq, 3): z = 0 Q -> Q^T and lse -> lseP,
-// z = 1 dO -> dO^T and Drow, z = 2 K -> K^T (blocks past B*Hk leave).
+// PRE-PASS. grid (Sp/64, B*Hq): Drow = rowsum(dO o O) and the copy of lse,
+// both padded to Sp (Drow 0, lse 0 past S-1). 16-byte pieces, DH/8 lanes per
+// row.
 // ---------------------------------------------------------------------------
 template <int DH>
 __launch_bounds__(256)
 __global__ void bwd_preprocess(
-    const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ dout, const short* __restrict__ out,
     const float* __restrict__ lse,  // [B,Hq,S]
-    short* __restrict__ qT, short* __restrict__ doT, short* __restrict__ kT,
     float* __restrict__ drowP, float* __restrict__ lseP,  // [B,Hq,Sp]
-    int B, int S, int Sp, int Hq, int Hk) {
+    int B, int S, int Sp, int Hq) {
   constexpr int PPR = DH / 8;  // 16-byte pieces per row
-  __shared__ unsigned int t[PT][DH / 2 + 1];
-
-  const int z = blockIdx.z;
-  const int H = (z == 2) ? Hk : Hq;
   const int bh = blockIdx.y;
-  if (bh >= B * H) return;
-  const int b = bh / H;
-  const int h = bh % H;
+  const int b = bh / Hq;
+  const int h = bh % Hq;
   const int s0 = blockIdx.x * PT;
-  const short* src = (z == 0) ? q : (z == 1) ? dout : k;
-  short* dst = (z == 0) ? qT : (z == 1) ? doT : kT;
 
   for (int i = threadIdx.x; i < PT * PPR; i += 256) {
     const int row = i / PPR;
     const int c = i % PPR;
     const int s = s0 + row;
-    const long long off = (((long long)b * S + s) * H + h) * DH + c * 8;
+    const long long off = (((long long)b * S + s) * Hq + h) * DH + c * 8;
     u32x4_t x = {0u, 0u, 0u, 0u};
-    if (s < S) x = *reinterpret_cast<const u32x4_t*>(src + off);
+    u32x4_t o = {0u, 0u, 0u, 0u};
+    if (s < S) {
+      x = *reinterpret_cast<const u32x4_t*>(dout + off);
+      o = *reinterpret_cast<const u32x4_t*>(out + off);
+    }
+    float acc = 0.f;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) t[row][c * 4 + w] = x[w];
-    if (z == 1) {
-      u32x4_t o = {0u, 0u, 0u, 0u};
-      if (s < S) o = *reinterpret_cast<const u32x4_t*>(out + off);
-      float acc = 0.f;
+    for (int w = 0; w < 4; ++w)
+      acc += bf2f((short)(x[w] & 0xffff)) * bf2f((short)(o[w] & 0xffff)) +
+             bf2f((short)(x[w] >> 16)) * bf2f((short)(o[w] >> 16));
 #pragma unroll
-      for (int w = 0; w < 4; ++w)
-        acc += bf2f((short)(x[w] & 0xffff)) * bf2f((short)(o[w] & 0xffff)) +
-               bf2f((short)(x[w] >> 16)) * bf2f((short)(o[w] >> 16));
-#pragma unroll
-      for (int m = PPR / 2; m > 0; m >>= 1) acc += __shfl_xor(acc, m, WAVE);
-      if (c == 0) drowP[((long long)b * Hq + h) * Sp + s] = acc;
-    } else if (z == 0 && c == 0) {
+    for (int m = PPR / 2; m > 0; m >>= 1) acc += __shfl_xor(acc, m, WAVE);
+    if (c == 0) {
       float l = 0.f;
       if (s < S) {
         l = lse[((long long)b * Hq + h) * S + s];
@@ -126,36 +120,18 @@ __global__ void bwd_preprocess(
         // instead makes its P exp(-inf) = 0, not exp(-inf - -inf) = NaN
         if (l == -INFINITY) l = INFINITY;
       }
+      drowP[((long long)b * Hq + h) * Sp + s] = acc;
       lseP[((long long)b * Hq + h) * Sp + s] = l;
     }
   }
-  __syncthreads();
-  // [D][64 s] out: 8 pieces of 16 B per d row, consecutive lanes along s
-  for (int i = threadIdx.x; i < DH * (PT / 8); i += 256) {
-    const int d = i / (PT / 8);
-    const int pc = i % (PT / 8);
-    const int sh = (d & 1) * 16;
-    unsigned int e[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) e[j] = (t[pc * 8 + j][d >> 1] >> sh) & 0xffffu;
-    u32x4_t y = {e[0] | (e[1] << 16), e[2] | (e[3] << 16),
-                 e[4] | (e[5] << 16), e[6] | (e[7] << 16)};
-    *reinterpret_cast<u32x4_t*>(dst + (((long long)b * H + h) * DH + d) * Sp +
-                                s0 + pc * 8) = y;
-  }
 }
 
 // ---------------------------------------------------------------------------
-// LDS images of one 32-row step. Row-major [32][DH] with the ((row&7)<<4)
-// XOR; transposed [DH][32] (64-byte rows) with the granule XOR (d>>2)&3.
-// Each is DH/16 wave-segments of 1024 B (64 lanes x 16 B, LDS-linear), so
-// the swizzles are applied to the per-lane SOURCE address.
+// LDS images of one 32-row step: row-major [32][DH] in the layout of
+// flash_bwd_layout.h, which serves the 16-byte row reads and the hardware
+// transposed reads alike. An image is DH/16 wave-segments of 1024 B (64 lanes
+// x 16 B, LDS-linear), so the XOR is applied to the per-lane SOURCE address.
 // ---------------------------------------------------------------------------
-template <int DH>
-DEV_INLINE int rmswz(int row, int byte_off) {
-  return row * (DH * 2) + (byte_off ^ ((row & 7) << 4));
-}
-
 DEV_INLINE void lds_dma16(const short* src, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds(
       reinterpret_cast<const unsigned int*>(src),
@@ -167,39 +143,60 @@ template <int DH>
 DEV_INLINE void issue_rm(const short* base, long long rs, int r0, int S,
                          char* img, int sseg, int lane) {
   const int linear = sseg * 1024 + lane * 16;
-  const int row = linear / (DH * 2);
-  const int colbyte = linear % (DH * 2);
-  const int src_col = colbyte ^ ((row & 7) << 4);
-  const int grow = r0 + row;
+  const int src_col = bwd_layout::dma_src_byte<DH>(linear);
+  const int grow = r0 + bwd_layout::dma_row<DH>(linear);
   const int srow = grow < S ? grow : S - 1;
   lds_dma16(base + (long long)srow * rs + (src_col >> 1), img + sseg * 1024);
-}
-
-// columns c0..c0+31 of a [DH][Sp] transposed image (always inside Sp)
-template <int DH>
-DEV_INLINE void issue_tr(const short* baseT, int Sp, int c0, char* img,
-                         int sseg, int lane) {
-  const int linear = sseg * 1024 + lane * 16;
-  const int d = linear >> 6;
-  const int g = ((linear >> 4) & 3) ^ ((d >> 2) & 3);
-  lds_dma16(baseT + (long long)d * Sp + c0 + g * 8, img + sseg * 1024);
 }
 
 // A (or B) fragment, natural k order: T[row][32*ks + 8*l4 .. +7]
 template <int DH>
 DEV_INLINE bf16x8_t read_rm(const char* img, int row, int ks, int l4) {
   return *reinterpret_cast<const bf16x8_t*>(
-      img + rmswz<DH>(row, (l4 * 8 + 32 * ks) * 2));
+      img + bwd_layout::img_off<DH>(row, (l4 * 8 + 32 * ks) * 2));
 }
 
-// A fragment in accumulator-pair k order: T^T[d][4*l4 .. +3, 16+4*l4 .. +3]
-DEV_INLINE bf16x8_t read_tr(const char* img, int d, int l4) {
-  const int sw = (d >> 2) & 3;
-  const char* rowp = img + d * 64 + (l4 & 1) * 8;
-  u32x2_t lo = *reinterpret_cast<const u32x2_t*>(rowp + (((l4 >> 1) ^ sw) << 4));
-  u32x2_t hi =
-      *reinterpret_cast<const u32x2_t*>(rowp + (((2 + (l4 >> 1)) ^ sw) << 4));
-  u32x4_t w = {lo[0], lo[1], hi[0], hi[1]};
+// A fragment in accumulator-pair k order, taken from the ROW-MAJOR image by
+// two ds_read_b64_tr_b16: T^T[16*dt + l15][4*l4 .. +3, 16+4*l4 .. +3].
+// The reads are inline assembly: through the builtin the compiler takes them
+// to alias the LDS-DMA writes of the steps in flight and puts s_waitcnt
+// vmcnt(0) in front, which undoes the ring. It therefore does not count them
+// either: tr_wait<N>() is the s_waitcnt lgkmcnt(N) before a fragment's use,
+// and it takes the fragment so that the use cannot move above it.
+// They need EXEC all ones: wave-uniform control flow only.
+DEV_INLINE unsigned lds_addr(const char* p) {
+  return (unsigned)(size_t)(
+      (const __attribute__((address_space(3))) char*)p);
+}
+
+struct tr_frag {
+  u32x2_t lo, hi;
+};
+
+template <int DH>
+DEV_INLINE tr_frag issue_tr_read(unsigned img, int dt, int lane) {
+  tr_frag f;
+  const unsigned a0 = img + bwd_layout::tr_read_addr<DH>(lane, dt, 0);
+  const unsigned a1 = img + bwd_layout::tr_read_addr<DH>(lane, dt, 1);
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.lo) : "v"(a0) : "memory");
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.hi) : "v"(a1) : "memory");
+  return f;
+}
+
+template <int N>
+DEV_INLINE void tr_wait(tr_frag& a, tr_frag& b) {
+  asm volatile("s_waitcnt lgkmcnt(%4)"
+               : "+v"(a.lo), "+v"(a.hi), "+v"(b.lo), "+v"(b.hi)
+               : "n"(N));
+}
+
+template <int N>
+DEV_INLINE void tr_wait(tr_frag& a) {
+  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a.lo), "+v"(a.hi) : "n"(N));
+}
+
+DEV_INLINE bf16x8_t tr_operand(const tr_frag& f) {
+  u32x4_t w = {f.lo[0], f.lo[1], f.hi[0], f.hi[1]};
   return __builtin_bit_cast(bf16x8_t, w);
 }
 
@@ -249,8 +246,6 @@ __global__ void flash_bwd_dkv_kernel(
     const short* __restrict__ k,     // [B,S,Hk,D]
     const short* __restrict__ v,     // [B,S,Hk,D]
     const short* __restrict__ dout,  // [B,S,Hq,D]
-    const short* __restrict__ qT,    // [B,Hq,D,Sp]
-    const short* __restrict__ doT,   // [B,Hq,D,Sp]
     const float* __restrict__ lseP,  // [B,Hq,Sp]
     const float* __restrict__ drowP,  // [B,Hq,Sp]
     const float* __restrict__ kvmask,  // [B,S] or null
@@ -265,12 +260,15 @@ __global__ void flash_bwd_dkv_kernel(
   constexpr int SPI = DH / 16;        // 1 KiB segments per image
   constexpr int NW = 8 / KTW;         // waves
   constexpr int WRK = 16 * KTW;       // keys per wave
-  constexpr int LD_OFF = 4 * IMG;     // lse[32], Drow[32]
+  constexpr int LD_OFF = 2 * IMG;     // lse[32], Drow[32]
   constexpr int BUF = LD_OFF + 256;
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
 
   const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
+  // in a scalar register: the branches on it below (the skipped strips, the
+  // counted waits) are then scalar branches and EXEC stays all ones around
+  // the transposed reads
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int l15 = lane & 15;
   const int l4 = lane >> 4;
 
@@ -304,6 +302,18 @@ __global__ void flash_bwd_dkv_kernel(
     }
     maskv[kt] = (kvmask && krow < S) ? kvmask[(long long)b * S + krow] : 0.f;
   }
+  // Consume them here, before the first DMA is issued: the compiler then
+  // waits for these loads now, not with a vmcnt(0) at their first use inside
+  // the loop, where it would also wait for the steps in flight.
+#pragma unroll
+  for (int kt = 0; kt < KTW; ++kt) {
+#pragma unroll
+    for (int ks_i = 0; ks_i < NKS; ++ks_i) {
+      asm volatile("" : "+v"(kfrag[kt][ks_i]));
+      asm volatile("" : "+v"(vfrag[kt][ks_i]));
+    }
+    asm volatile("" : "+v"(maskv[kt]));
+  }
 
   f32x4_t dk_acc[NDT][KTW], dv_acc[NDT][KTW];
 #pragma unroll
@@ -318,20 +328,17 @@ __global__ void flash_bwd_dkv_kernel(
   const int nq = (S - q_start + TS - 1) / TS;
   const int total = G * nq;
 
-  // one step's loads: Q, dO row-major, Q^T, dO^T, lse/Drow
+  static_assert(SPI <= NW, "one image segment per wave at the most");
+  // one step's loads: the Q and dO images, lse/Drow
   auto issue = [&](int g, int qb, int bufi) {
     const int h = hk * G + g;
     char* buf = smem + bufi * BUF;
     const short* qp = q + ((long long)b * S) * qrs + h * DH;
     const short* dop = dout + ((long long)b * S) * qrs + h * DH;
-    const long long toff = ((long long)b * Hq + h) * DH * Sp;
     const long long roff = ((long long)b * Hq + h) * Sp;
-#pragma unroll
-    for (int sseg = wave; sseg < SPI; sseg += NW) {
-      issue_rm<DH>(qp, qrs, qb, S, buf, sseg, lane);
-      issue_rm<DH>(dop, qrs, qb, S, buf + IMG, sseg, lane);
-      issue_tr<DH>(qT + toff, Sp, qb, buf + 2 * IMG, sseg, lane);
-      issue_tr<DH>(doT + toff, Sp, qb, buf + 3 * IMG, sseg, lane);
+    if (wave < SPI) {
+      issue_rm<DH>(qp, qrs, qb, S, buf, wave, lane);
+      issue_rm<DH>(dop, qrs, qb, S, buf + IMG, wave, lane);
     }
     if (wave == 0) {
       const float* s = (lane < 32 ? lseP : drowP) + roff + qb + (lane & 31);
@@ -346,9 +353,12 @@ __global__ void flash_bwd_dkv_kernel(
   for (int it = 0; it < total; ++it) {
     const int qb = qb_nx;
     // this step's loads (the only ones in flight) have landed; after the
-    // barrier every wave is also done reading the other buffer
+    // barrier every wave is also done reading the other buffer. The bare
+    // barrier, not __syncthreads(): every LDS read of step it-1 was waited
+    // for before its MFMA, and the wait above is the only fence needed.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
     qb_nx += TS;
     if (qb_nx >= S) {
       qb_nx = q_start;
@@ -429,11 +439,24 @@ __global__ void flash_bwd_dkv_kernel(
     }
 
     // ---- dV^T += dO^T P ; dK^T += Q^T dS --------------------------------
+    // A operands by transposed reads of the two row-major images, one d-tile
+    // ahead of the MFMAs that use them
+    const unsigned qimg = lds_addr(buf);
+    tr_frag fq[2], fd[2];
+    fq[0] = issue_tr_read<DH>(qimg, 0, lane);
+    fd[0] = issue_tr_read<DH>(qimg + IMG, 0, lane);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) {
-      bf16x8_t aqt = read_tr(buf + 2 * IMG, l15 + 16 * dt, l4);
-      bf16x8_t adt = read_tr(buf + 3 * IMG, l15 + 16 * dt, l4);
+      if (dt + 1 < NDT) {
+        fq[(dt + 1) & 1] = issue_tr_read<DH>(qimg, dt + 1, lane);
+        fd[(dt + 1) & 1] = issue_tr_read<DH>(qimg + IMG, dt + 1, lane);
+        tr_wait<4>(fq[dt & 1], fd[dt & 1]);
+      } else {
+        tr_wait<0>(fq[dt & 1], fd[dt & 1]);
+      }
+      const bf16x8_t aqt = tr_operand(fq[dt & 1]);
+      const bf16x8_t adt = tr_operand(fd[dt & 1]);
 #pragma unroll
       for (int kt = 0; kt < KTW; ++kt) {
         dv_acc[dt][kt] =
@@ -474,7 +497,6 @@ __launch_bounds__(256, 2)
 __global__ void flash_bwd_dq_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
     const short* __restrict__ v, const short* __restrict__ dout,
-    const short* __restrict__ kT,     // [B,Hk,D,Sp]
     const float* __restrict__ lseP,   // [B,Hq,Sp]
     const float* __restrict__ drowP,  // [B,Hq,Sp]
     const float* __restrict__ kvmask,  // [B,S] or null
@@ -487,7 +509,7 @@ __global__ void flash_bwd_dq_kernel(
   constexpr int IMG = TS * DH * 2;
   constexpr int SPI = DH / 16;
   constexpr int IPI = SPI / 4;
-  constexpr int BUF = 3 * IMG;  // K, V row-major, K^T
+  constexpr int BUF = 2 * IMG;  // K, V
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
 
   const int lane = threadIdx.x & 63;
@@ -510,7 +532,6 @@ __global__ void flash_bwd_dq_kernel(
   const short* dop = dout + ((long long)b * S) * qrs + h * DH;
   const short* kp = k + ((long long)b * S) * kvrs + hk * DH;
   const short* vp = v + ((long long)b * S) * kvrs + hk * DH;
-  const short* ktp = kT + ((long long)b * Hk + hk) * DH * Sp;
   const float* mp = kvmask ? kvmask + (long long)b * S : nullptr;
 
   // Q and dO fragments in registers (B operands: q row on the lane), and
@@ -550,7 +571,6 @@ __global__ void flash_bwd_dq_kernel(
       const int sseg = i * 4 + wave;
       issue_rm<DH>(kp, kvrs, kvb, S, buf, sseg, lane);
       issue_rm<DH>(vp, kvrs, kvb, S, buf + IMG, sseg, lane);
-      issue_tr<DH>(ktp, Sp, kvb, buf + 2 * IMG, sseg, lane);
     }
   };
 
@@ -628,10 +648,20 @@ __global__ void flash_bwd_dq_kernel(
       dsb[qt] = pack_pair(dp_acc[0][qt], dp_acc[1][qt]);
 
     // ---- dQ^T += K^T dS^T -------------------------------------------------
+    // K^T by transposed reads of the row-major K image, one d-tile ahead
+    const unsigned kimg = lds_addr(buf);
+    tr_frag fk[2];
+    fk[0] = issue_tr_read<DH>(kimg, 0, lane);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) {
-      bf16x8_t akt = read_tr(buf + 2 * IMG, l15 + 16 * dt, l4);
+      if (dt + 1 < NDT) {
+        fk[(dt + 1) & 1] = issue_tr_read<DH>(kimg, dt + 1, lane);
+        tr_wait<2>(fk[dt & 1]);
+      } else {
+        tr_wait<0>(fk[dt & 1]);
+      }
+      const bf16x8_t akt = tr_operand(fk[dt & 1]);
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt)
         dq_acc[dt][qt] =
@@ -665,11 +695,9 @@ static void launch_bwd(at::Tensor& q, at::Tensor& k, at::Tensor& v,
                        int B, int S, int Hq, int Hk, float scale,
                        int causal) {
   auto stream = c10::hip::getCurrentHIPStream();
-  // scratch, fully rewritten (pad included) by the pre-pass of every call
+  // row constants, fully rewritten (pad included) by the pre-pass of every
+  // call: the only scratch left
   const int Sp = (S + bwd::BR - 1) / bwd::BR * bwd::BR;
-  auto qT = at::empty({B, Hq, DH, Sp}, q.options());
-  auto doT = at::empty({B, Hq, DH, Sp}, q.options());
-  auto kT = at::empty({B, Hk, DH, Sp}, q.options());
   auto drow = at::empty({B, Hq, Sp}, q.options().dtype(at::kFloat));
   auto lseP = at::empty({B, Hq, Sp}, q.options().dtype(at::kFloat));
   auto sp = [](const at::Tensor& t) {
@@ -678,23 +706,22 @@ static void launch_bwd(at::Tensor& q, at::Tensor& k, at::Tensor& v,
   auto spm = [](at::Tensor& t) {
     return reinterpret_cast<short*>(t.data_ptr());
   };
-  dim3 grid0(Sp / bwd::PT, B * Hq, 3);
+  dim3 grid0(Sp / bwd::PT, B * Hq);
   hipLaunchKernelGGL(bwd::bwd_preprocess<DH>, grid0, dim3(256), 0,
-                     stream.stream(), sp(q), sp(k), sp(dout), sp(out),
-                     lse.data_ptr<float>(), spm(qT), spm(doT), spm(kT),
-                     drow.data_ptr<float>(), lseP.data_ptr<float>(), B, S,
-                     Sp, Hq, Hk);
+                     stream.stream(), sp(dout), sp(out),
+                     lse.data_ptr<float>(), drow.data_ptr<float>(),
+                     lseP.data_ptr<float>(), B, S, Sp, Hq);
   HIP_CHECK_KERNEL();
   dim3 grid1(Sp / bwd::BR, B * Hk);
   hipLaunchKernelGGL((bwd::flash_bwd_dkv_kernel<DH, bwd::KTW1, ROPE>), grid1,
                      dim3(512 / bwd::KTW1), 0, stream.stream(), sp(q), sp(k),
-                     sp(v), sp(dout), sp(qT), sp(doT), lseP.data_ptr<float>(),
+                     sp(v), sp(dout), lseP.data_ptr<float>(),
                      drow.data_ptr<float>(), mp, spm(dk), spm(dv), cosp, sinp,
                      B, S, Sp, Hq, Hk, scale, causal);
   HIP_CHECK_KERNEL();
   dim3 grid2(Sp / bwd::BR, B * Hq);
   hipLaunchKernelGGL((bwd::flash_bwd_dq_kernel<DH, ROPE>), grid2, dim3(256), 0,
-                     stream.stream(), sp(q), sp(k), sp(v), sp(dout), sp(kT),
+                     stream.stream(), sp(q), sp(k), sp(v), sp(dout),
                      lseP.data_ptr<float>(), drow.data_ptr<float>(), mp,
                      spm(dq), cosp, sinp, B, S, Sp, Hq, Hk, scale, causal);
   HIP_CHECK_KERNEL();
