@@ -46,11 +46,16 @@ def _fp8_ok(x, w):
 
 
 def _quant(t, dtype, fmax):
-    """Per-tensor dynamic scale: t = t8 * scale (torch-op fallback)."""
-    amax = torch.linalg.vector_norm(t.detach(), float("inf")) \
-        .float().clamp(min=1e-12)
-    scale = (amax / fmax)
-    t8 = (t * scale.reciprocal().to(t.dtype)).clamp(-fmax, fmax).to(dtype)
+    """Per-tensor dynamic scale: t = t8 * scale (torch-op fallback).
+
+    The arithmetic of the HIP kernels, in fp32 whatever t's dtype: the
+    reciprocal of an fp16 scale overflows to inf for amax < fmax / 65504
+    (every realistic dy), and one rounded to bf16 moves ~4 % of the codes,
+    so the two arms of _quant_hip would disagree on the same tensor."""
+    amax = torch.linalg.vector_norm(t.detach(), float("inf")).float()
+    scale = (amax / fmax).clamp(min=1e-12)
+    inv = 1.0 / scale
+    t8 = (t.detach().float() * inv).clamp(-fmax, fmax).to(dtype)
     return t8, scale
 
 

@@ -94,9 +94,9 @@ def test_fp8_quant_kernels_match_torch():
     """HIP amax/cast/cast_transpose equal the torch-op formula bit for bit:
     amax == x.abs().amax(), codes == (x.float() * inv).clamp(-fmax, fmax)
     cast by torch, inv = 1 / max(scale, 1e-12) in fp32 -- the arithmetic the
-    kernels perform, so no code may differ. (_quant divides by the scale
-    instead of multiplying by its reciprocal; that alone moves ~2 % of the
-    codes by one step and is no property of the kernels.)"""
+    kernels perform, so no code may differ. (_quant, the torch fallback, does
+    the same arithmetic; test_fp8_linear_gpu.py holds the two arms of
+    _quant_hip to the same bits.)"""
     from deepspeed_amd.ops.loader import get_ext
     from deepspeed_amd.ops.fp8_linear import E4M3_MAX, E5M2_MAX
     ext = get_ext()
