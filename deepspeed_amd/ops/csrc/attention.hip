@@ -3,33 +3,26 @@
 // Role parity: reference uses CUTLASS/flash-attn kernels
 // (deepspeed/inference/v2/kernels, csrc/transformer/inference/csrc/softmax.cu).
 // MI355X-native design (guide §B "fused attention prefill"): one kernel,
-// flash_fwd_v5_kernel below — 8 waves/block, 256 q-rows per block (32 per
+// flash_fwd_v6_kernel below — 8 waves/block, 256 q-rows per block (32 per
 // wave), KV tiles of 64, mfma_f32_32x32x16_bf16, online softmax in fp32
 // registers, causal and additive kv-column masking, GQA via head-group
 // indexing; saves per-row LSE for the backward pass.
 // A q row with no admissible kv column (fully masked) yields out = 0 and
 // lse = -inf.
 // Correctness: elementwise against a float64 reference with derived bounds
-// (tests/test_attention_edges_gpu.py, references in tests/attn_refs.py).
+// (tests/test_attention_edges_gpu.py, tests/test_flash_fwd_vimage_gpu.py,
+// references in tests/attn_refs.py); the LDS layout is proven on the CPU
+// (tests/test_flash_fwd_layout_cpu.py).
 #include <torch/extension.h>
 
 #include "common.h"
+#include "flash_fwd_layout.h"
+#include "lds_tr_read.h"
 
 using bf16x8_t = __attribute__((ext_vector_type(8))) short;
 
-constexpr int KVTILE = 64;  // kv rows per tile
-constexpr int VT_PAD = 8;   // Vt rows padded: [DH][64+8]
-
-// Vt[d][kv] byte offset: pad-8 rows spread the d-read (2-way) and the
-// ((d>>5)&3)<<5 XOR spreads the 4 d-groups on the transpose write
-// (was an 8-way write conflict -> ~2-way). Alignment: both terms are
-// multiples of 16B for the b128 reads.
-DEV_INLINE int vtswz(int d, int kv_byte) {
-  return d * ((KVTILE + VT_PAD) * 2) + (kv_byte ^ (((d >> 5) & 3) << 5));
-}
-
 // ===========================================================================
-// v5: 8-wave 32x32 "swapped QK^T" forward (guide §B 8-warp ladder).
+// v6: 8-wave 32x32 "swapped QK^T" forward (guide §B 8-warp ladder).
 //   - each wave owns 32 q rows (block = 256 q rows), KV tiles of 64
 //   - S^T = K·Q^T via mfma_f32_32x32x16_bf16: C col = q = lane&31, so the
 //     softmax row (over kv) is LANE-LOCAL: in-lane reduce + one half-swap
@@ -37,7 +30,15 @@ DEV_INLINE int vtswz(int d, int kv_byte) {
 //     the PV A/B fragments directly — no P LDS staging, no cross-wave sync
 //   - PV computed as O^T = V^T·P^T so O's q is also lane-local and the
 //     online-softmax rescale is a scalar multiply
-//   - K staged via global_load_lds (pre-swizzled source), V transposed
+//   - K and V each have ONE row-major [64][DH] LDS image per tile, both
+//     filled by global_load_lds (pre-swizzled source column) into a double
+//     buffer: tile t+1 is in flight while tile t computes, one barrier per
+//     tile. K is read by rows (ds_read_b128); V's MFMA operand is read
+//     TRANSPOSED in hardware (ds_read_b64_tr_b16, lds_tr_read.h), one d-tile
+//     ahead of its MFMAs. No transposed copy of V is made. The layout, with
+//     its bank-conflict argument (both reads degree 1), is flash_fwd_layout.h.
+//   - image rows past S-1 repeat row S-1 (nothing outside q, k, v is read);
+//     their score is -inf, so their P is exactly 0.
 // C/D layout (32x32x16): col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5).
 // A/B operand: row(col)=lane&31, k=(lane>>5)*8+j.
 // ===========================================================================
@@ -63,17 +64,31 @@ DEV_INLINE unsigned int cvtpk2(float lo, float hi) {
   return (unsigned int)a | ((unsigned int)b << 16);
 }
 
-// swizzled row-major byte offset for a [R][DH] bf16 tile
+static_assert(KT5 == fwd_layout::KT, "the image layout is for 64-key tiles");
+
+// 16 bytes per lane, global -> LDS; the wave's 64 pieces land LDS-linear
+DEV_INLINE void fwd_dma16(const short* src, char* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds(
+      reinterpret_cast<const unsigned int*>(src),
+      reinterpret_cast<unsigned int*>(lds_wave_base), 16, 0, 0);
+}
+
+// the 4 k-slices x 2 halves of V's operand for one d-tile: one base register,
+// the (ks, hf) constants of the layout in the offset field
 template <int DH>
-DEV_INLINE int kswz_t(int row, int byte_off) {
-  return row * (DH * 2) + (byte_off ^ ((row & 7) << 4));
+DEV_INLINE void issue_v_dtile(tr_frag (&f)[4], unsigned base) {
+  using namespace fwd_layout;
+  f[0] = issue_tr_read_off<v_tr_step<DH>(0, 0), v_tr_step<DH>(0, 1)>(base);
+  f[1] = issue_tr_read_off<v_tr_step<DH>(1, 0), v_tr_step<DH>(1, 1)>(base);
+  f[2] = issue_tr_read_off<v_tr_step<DH>(2, 0), v_tr_step<DH>(2, 1)>(base);
+  f[3] = issue_tr_read_off<v_tr_step<DH>(3, 0), v_tr_step<DH>(3, 1)>(base);
 }
 
 // kvmask: optional [B,S] additive float mask over kv columns (padding
 // masks, ALiBi-free BERT-class workloads); nullptr = none.
 template <int DH>
 __launch_bounds__(512, 2)
-__global__ void flash_fwd_v5_kernel(
+__global__ void flash_fwd_v6_kernel(
     const short* __restrict__ q,  // [B,S,Hq,D]
     const short* __restrict__ k,  // [B,S,Hk,D]
     const short* __restrict__ v,  // [B,S,Hk,D]
@@ -81,14 +96,16 @@ __global__ void flash_fwd_v5_kernel(
     float* __restrict__ lse_out,  // [B,Hq,S]
     const float* __restrict__ kvmask,  // [B,S] or null
     int B, int S, int Hq, int Hk, float scale, int causal) {
-  // K double-buffered: tile t+1's global_load_lds issues during tile t's
-  // compute (async-STAGE, guide T14); V global loads land in registers one
-  // tile early and scatter to LDS after the barrier.
-  __shared__ short k_lds[2][KT5 * DH];              // swizzled row-major
-  __shared__ short vt_lds[DH * (KT5 + VT_PAD)];     // transposed
+  // K and V double-buffered, one array: [K 0][K 1][V 0][V 1], each a
+  // row-major image of flash_fwd_layout.h. Tile t+1's global_load_lds issue
+  // before tile t's compute.
+  constexpr int IMG = KT5 * DH * 2;  // bytes per image
+  __shared__ __attribute__((aligned(16))) char smem[4 * IMG];
 
   const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
+  // in a scalar register: the LDS-DMA segment bases are then scalar and no
+  // branch on it can leave EXEC partial around the transposed reads
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int l31 = lane & 31;
   const int hi = lane >> 5;  // half-wave: 0 or 1
 
@@ -119,6 +136,11 @@ __global__ void flash_fwd_v5_kernel(
 #pragma unroll
     for (int ks = 0; ks < NQF; ++ks)
       qfrag[ks] = *reinterpret_cast<const bf16x8_t*>(src + 16 * ks);
+    // Consume them here, before the first DMA is issued: the compiler then
+    // waits for these loads now, not with a vmcnt(0) at their first use
+    // inside the loop, where it would also wait for the tile in flight.
+#pragma unroll
+    for (int ks = 0; ks < NQF; ++ks) asm volatile("" : "+v"(qfrag[ks]));
   }
 
   // softmax runs in the exp2 domain (v_exp_f32 is natively 2^x): S values
@@ -135,73 +157,43 @@ __global__ void flash_fwd_v5_kernel(
   const int kv_end = causal ? min(S, qbase + QT5) : S;
   const int n_tiles = (kv_end + KT5 - 1) / KT5;
 
-  // async-STAGE helpers -----------------------------------------------------
-  // V staging: DH/16 threads per row, 16 cols each (guard rows >= KT5 for
-  // DH < 128 where 512 threads cover more than one tile)
-  constexpr int VTPR = DH / 16;
-  const int st_row = threadIdx.x / VTPR;
-  const int st_c0 = (threadIdx.x % VTPR) * 16;
-  // K tile = KT5*DH*2 bytes in 1024-byte wave segments (64 lanes x 16 B)
-  constexpr int KSEGS = KT5 * DH * 2 / 1024;
-  constexpr int KPASSES = (KSEGS + 7) / 8;
+  // One tile's loads: an image is IMG/1024 wave segments of 1024 bytes (64
+  // lanes x 16 B, LDS-linear), so the layout's XOR is applied to the per-lane
+  // SOURCE column. Rows past S-1 repeat row S-1.
+  constexpr int SEGS = IMG / 1024;
+  static_assert(SEGS % 8 == 0, "whole passes of the 8 waves");
+  constexpr int PASSES = SEGS / 8;
+  auto issue_tile = [&](int t_) {
+    char* kimg_ = smem + (t_ & 1) * IMG;
+    char* vimg_ = smem + (2 + (t_ & 1)) * IMG;
+#pragma unroll
+    for (int pass = 0; pass < PASSES; ++pass) {
+      const int seg = pass * 8 + wave;
+      const int linear = seg * 1024 + lane * 16;
+      const int grow = t_ * KT5 + fwd_layout::dma_row<DH>(linear);
+      const int srow = grow < S ? grow : S - 1;
+      const long long roff = (long long)srow * kvrs;
+      fwd_dma16(kp + roff + (fwd_layout::k_dma_src_byte<DH>(linear) >> 1),
+                kimg_ + seg * 1024);
+      fwd_dma16(vp + roff + (fwd_layout::v_dma_src_byte<DH>(linear) >> 1),
+                vimg_ + seg * 1024);
+    }
+  };
 
-#define ISSUE_K(t_)                                                          \
-  {                                                                          \
-    int kvb_ = (t_)*KT5;                                                     \
-    short* kbuf_ = k_lds[(t_)&1];                                            \
-    for (int pass = 0; pass < KPASSES; ++pass) {                             \
-      int seg = pass * 8 + wave;                                             \
-      int linear = seg * 1024 + lane * 16;                                   \
-      int row = linear / (DH * 2);                                           \
-      int colbyte = linear % (DH * 2);                                       \
-      int src_col = colbyte ^ ((row & 7) << 4);                              \
-      int grow = kvb_ + row;                                                 \
-      int srow = grow < S ? grow : S - 1;                                    \
-      const short* src = kp + (long long)srow * kvrs + (src_col >> 1);       \
-      __builtin_amdgcn_global_load_lds(                                      \
-          reinterpret_cast<const unsigned int*>(src),                        \
-          reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(kbuf_) +   \
-                                          seg * 1024),                       \
-          16, 0, 0);                                                         \
-    }                                                                        \
-  }
-
-#define LOAD_V(t_, dst_)                                                     \
-  {                                                                          \
-    int grow = (t_)*KT5 + st_row;                                            \
-    const short* vrow = vp + (long long)grow * kvrs;                         \
-    if (st_row < KT5 && grow < S) {                                          \
-      dst_[0] = *reinterpret_cast<const bf16x8_t*>(vrow + st_c0);            \
-      dst_[1] = *reinterpret_cast<const bf16x8_t*>(vrow + st_c0 + 8);        \
-    } else {                                                                 \
-      dst_[0] = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};                            \
-      dst_[1] = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};                            \
-    }                                                                        \
-  }
-
-  bf16x8_t vreg[2], vnext[2];
-  ISSUE_K(0);
-  LOAD_V(0, vreg);
+  const unsigned smem_a = lds_addr(smem);
+  issue_tile(0);
 
   for (int t = 0; t < n_tiles; ++t) {
     const int kvbase = t * KT5;
-    const bool has_next = (t + 1) < n_tiles;
-    if (has_next) ISSUE_K(t + 1);  // lands in the other K buffer
-    // scatter this tile's V registers into LDS (the compiler's wait for
-    // vreg also retires this tile's older global_load_lds -> k_lds)
-    if (st_row < KT5) {
-      char* vbase = reinterpret_cast<char*>(vt_lds);
-#pragma unroll
-      for (int cc = 0; cc < 2; ++cc) {
-        int col = st_c0 + cc * 8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          *reinterpret_cast<short*>(vbase + vtswz(col + j, st_row * 2)) =
-              vreg[cc][j];
-      }
-    }
-    if (has_next) LOAD_V(t + 1, vnext);  // in flight under this tile's MFMAs
-    __syncthreads();
+    // This tile's loads (the only ones in flight) have landed; after the
+    // barrier every wave is also done reading the other buffers. The bare
+    // barrier: every LDS read of tile t-1 was waited for before its MFMA.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (t + 1 < n_tiles) issue_tile(t + 1);  // lands in the other buffers
+    const char* kimg = smem + (t & 1) * IMG;
+    const unsigned vimg = smem_a + (2 + (t & 1)) * IMG;
 
     // ---- S^T = K Q^T: st[mt] rows kv = kvbase+32mt+(r&3)+8*(r>>2)+4hi ---
     f32x16_t st[2];
@@ -211,17 +203,19 @@ __global__ void flash_fwd_v5_kernel(
       f32x16_t acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      int krow = 32 * mt + l31;
 #pragma unroll
       for (int ks = 0; ks < NQF; ++ks) {
         bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(
-            reinterpret_cast<char*>(k_lds[t & 1]) +
-            kswz_t<DH>(krow, (16 * ks + hi * 8) * 2));
+            kimg + fwd_layout::k_row_read_addr<DH>(lane, mt, ks));
         acc = MFMA_BF16_32x32x16(kf, qfrag[ks], acc, 0, 0, 0);
       }
       st[mt] = acc;
     }
     __builtin_amdgcn_s_setprio(0);
+
+    // V's operand for d-tile 0: the reads fly under the softmax
+    tr_frag vf[2][4];
+    issue_v_dtile<DH>(vf[0], vimg + fwd_layout::v_tr_lane_base<DH>(lane, 0));
 
     // ---- online softmax (lane-local q row) ------------------------------
     // btile is wave-uniform: interior tiles take the cmp-free path
@@ -309,25 +303,26 @@ __global__ void flash_fwd_v5_kernel(
     }
 
     // ---- O^T += V^T P^T  (4 d m-tiles x 4 kv k-slices) ------------------
+    // A operand V[16ks + 8hi + j][32mt + l31] by transposed reads of the
+    // row-major image, one d-tile (8 reads) ahead of the MFMAs that use them
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int mt = 0; mt < NOT; ++mt) {
-      int drow = 32 * mt + l31;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        bf16x8_t vf = *reinterpret_cast<const bf16x8_t*>(
-            reinterpret_cast<char*>(vt_lds) +
-            vtswz(drow, (16 * ks + hi * 8) * 2));
-        ot[mt] = MFMA_BF16_32x32x16(vf, pfrag[ks], ot[mt], 0, 0, 0);
+      if (mt + 1 < NOT) {
+        issue_v_dtile<DH>(
+            vf[(mt + 1) & 1],
+            vimg + fwd_layout::v_tr_lane_base<DH>(lane, mt + 1));
+        tr_wait<8>(vf[mt & 1]);
+      } else {
+        tr_wait<0>(vf[mt & 1]);
       }
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+        ot[mt] = MFMA_BF16_32x32x16(tr_operand(vf[mt & 1][ks]), pfrag[ks],
+                                    ot[mt], 0, 0, 0);
     }
     __builtin_amdgcn_s_setprio(0);
-    __syncthreads();
-    vreg[0] = vnext[0];
-    vreg[1] = vnext[1];
   }
-#undef ISSUE_K
-#undef LOAD_V
 
   // ---- epilogue: O^T lane holds d rows for its q col --------------------
   if (my_q < S) {
@@ -399,7 +394,7 @@ std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k,
   auto stream = c10::hip::getCurrentHIPStream();
   dim3 grid((S + QT5 - 1) / QT5, B * Hq);
   if (D == 128) {
-    hipLaunchKernelGGL(flash_fwd_v5_kernel<128>, grid, dim3(512), 0,
+    hipLaunchKernelGGL(flash_fwd_v6_kernel<128>, grid, dim3(512), 0,
                        stream.stream(),
                        reinterpret_cast<const short*>(q.data_ptr()),
                        reinterpret_cast<const short*>(k.data_ptr()),
@@ -408,7 +403,7 @@ std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k,
                        lse.data_ptr<float>(), mp, B, S, Hq, Hk, fscale,
                        causal ? 1 : 0);
   } else {
-    hipLaunchKernelGGL(flash_fwd_v5_kernel<64>, grid, dim3(512), 0,
+    hipLaunchKernelGGL(flash_fwd_v6_kernel<64>, grid, dim3(512), 0,
                        stream.stream(),
                        reinterpret_cast<const short*>(q.data_ptr()),
                        reinterpret_cast<const short*>(k.data_ptr()),

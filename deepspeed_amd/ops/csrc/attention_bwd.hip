@@ -49,6 +49,7 @@
 
 #include "common.h"
 #include "flash_bwd_layout.h"
+#include "lds_tr_read.h"
 
 using bf16x8_t = __attribute__((ext_vector_type(8))) short;
 using f32x4_t = __attribute__((ext_vector_type(4))) float;
@@ -158,46 +159,13 @@ DEV_INLINE bf16x8_t read_rm(const char* img, int row, int ks, int l4) {
 
 // A fragment in accumulator-pair k order, taken from the ROW-MAJOR image by
 // two ds_read_b64_tr_b16: T^T[16*dt + l15][4*l4 .. +3, 16+4*l4 .. +3].
-// The reads are inline assembly: through the builtin the compiler takes them
-// to alias the LDS-DMA writes of the steps in flight and puts s_waitcnt
-// vmcnt(0) in front, which undoes the ring. It therefore does not count them
-// either: tr_wait<N>() is the s_waitcnt lgkmcnt(N) before a fragment's use,
-// and it takes the fragment so that the use cannot move above it.
-// They need EXEC all ones: wave-uniform control flow only.
-DEV_INLINE unsigned lds_addr(const char* p) {
-  return (unsigned)(size_t)(
-      (const __attribute__((address_space(3))) char*)p);
-}
-
-struct tr_frag {
-  u32x2_t lo, hi;
-};
-
+// The reads, their counted waits (tr_wait<N>) and tr_operand are in
+// lds_tr_read.h, with the reasons they are inline assembly. They need EXEC
+// all ones: wave-uniform control flow only.
 template <int DH>
 DEV_INLINE tr_frag issue_tr_read(unsigned img, int dt, int lane) {
-  tr_frag f;
-  const unsigned a0 = img + bwd_layout::tr_read_addr<DH>(lane, dt, 0);
-  const unsigned a1 = img + bwd_layout::tr_read_addr<DH>(lane, dt, 1);
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.lo) : "v"(a0) : "memory");
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.hi) : "v"(a1) : "memory");
-  return f;
-}
-
-template <int N>
-DEV_INLINE void tr_wait(tr_frag& a, tr_frag& b) {
-  asm volatile("s_waitcnt lgkmcnt(%4)"
-               : "+v"(a.lo), "+v"(a.hi), "+v"(b.lo), "+v"(b.hi)
-               : "n"(N));
-}
-
-template <int N>
-DEV_INLINE void tr_wait(tr_frag& a) {
-  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a.lo), "+v"(a.hi) : "n"(N));
-}
-
-DEV_INLINE bf16x8_t tr_operand(const tr_frag& f) {
-  u32x4_t w = {f.lo[0], f.lo[1], f.hi[0], f.hi[1]};
-  return __builtin_bit_cast(bf16x8_t, w);
+  return ::issue_tr_read(img + bwd_layout::tr_read_addr<DH>(lane, dt, 0),
+                       img + bwd_layout::tr_read_addr<DH>(lane, dt, 1));
 }
 
 // two accumulator tiles (rows 0..15 and 16..31 of the summed index) -> the

@@ -15,8 +15,10 @@
 // Shape: grid (ceil(max_qlen/32), n, Hq), 4 waves per block. A block owns one
 // 32-token q tile of one sequence and one q head; its waves split the KV
 // tiles of 64 (wave w takes tiles w, w+4, ...) and merge (m, l, O) in LDS the
-// way ragged_decode_kernel does. Fragment layouts, the in-register P build and
-// the V-transpose staging are those documented at the top of attention.hip:
+// way ragged_decode_kernel does. Fragment layouts and the in-register P build
+// are those documented at the top of attention.hip; V is transposed by hand
+// into a padded [D][64+8] image (vtswz below), as the training forward did
+// before it moved to hardware-transposed reads:
 //   S^T = K Q^T  (C col = q = lane&31, so the softmax row is lane-local),
 //   O^T = V^T P^T with V^T staged per wave in LDS.
 // K fragments are read straight from the pool (a lane's 8 k-values are 16
@@ -42,7 +44,8 @@ constexpr int NW = 4;       // waves per block
 constexpr int VT_PAD = 8;   // Vt rows padded: [D][64+8]
 constexpr int OPAD = 4;     // merge rows padded: [32][D+4] floats
 
-// Vt[d][kv] byte offset (same swizzle as attention.hip)
+// Vt[d][kv] byte offset: pad-8 rows spread the d-read and the ((d>>5)&3)<<5
+// XOR spreads the 4 d-groups on the transpose write (~2-way)
 DEV_INLINE int vtswz(int d, int kv_byte) {
   return d * ((KT + VT_PAD) * 2) + (kv_byte ^ (((d >> 5) & 3) << 5));
 }

@@ -36,7 +36,7 @@ constexpr int NW = 4;       // waves per block
 constexpr int VT_PAD = 8;   // Vt rows padded: [D][64+8]
 constexpr int OPAD = 4;     // merge rows padded: [32][D+4] floats
 
-// Vt[d][kv] byte offset (same swizzle as attention.hip)
+// Vt[d][kv] byte offset (same swizzle as ragged_prefill.hip)
 DEV_INLINE int vtswz(int d, int kv_byte) {
   return d * ((KT + VT_PAD) * 2) + (kv_byte ^ (((d >> 5) & 3) << 5));
 }

@@ -14,7 +14,8 @@ mask.
 
 Environment: AB_B (1), AB_S (4096), AB_D (128), AB_HQ (32), AB_HK (8),
 AB_CAUSAL (1), AB_ITERS (20, at least 20 are run), AB_BWD_ONLY (0: set to 1
-to skip the forward and SDPA timings).
+to skip the forward and SDPA timings), AB_FWD_ONLY (0: set to 1 to time
+`flash_attn_fwd` alone, min and median, and nothing else).
 """
 import math
 import os
@@ -33,6 +34,7 @@ Hk = int(os.environ.get("AB_HK", 8))
 CAUSAL = bool(int(os.environ.get("AB_CAUSAL", 1)))
 ITERS = max(20, int(os.environ.get("AB_ITERS", 20)))
 BWD_ONLY = bool(int(os.environ.get("AB_BWD_ONLY", 0)))
+FWD_ONLY = bool(int(os.environ.get("AB_FWD_ONLY", 0)))
 WARMUP = 5
 
 
@@ -67,6 +69,15 @@ def main():
     product = 2.0 * B * Hq * S * S * D * (0.5 if CAUSAL else 1.0)
     print(f"shape: B {B} S {S} Hq {Hq} Hk {Hk} D {D} "
           f"{'causal' if CAUSAL else 'full'}, {ITERS} timed calls")
+
+    if FWD_ONLY:
+        with torch.no_grad():
+            t_min, t_med = bench(
+                lambda: ext.flash_attn_fwd(q, k, v, CAUSAL, scale))
+        print(f"fwd only: min {t_min:8.3f} ms  median {t_med:8.3f} ms")
+        print(f"fwd only: {2 * product / t_min / 1e9:7.1f} TF/s "
+              f"(2 products), at min")
+        return
 
     with torch.no_grad():
         out, lse = ext.flash_attn_fwd(q, k, v, CAUSAL, scale)
