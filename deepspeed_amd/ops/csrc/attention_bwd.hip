@@ -11,9 +11,11 @@
 // the pad is written as zeros, so every read of them is in bounds. They are
 // the only scratch: no transposed copy of Q, dO or K exists.
 //
-// Both passes have the same shape: a workgroup owns 128 rows of its outer
-// index (pass 1: 8 waves x 16 keys; pass 2: 4 waves x 32 q rows) and streams
-// the other index in steps of 32.
+// Both passes have the same shape: a workgroup of 4 waves owns a block of
+// its outer index (pass 1: 4 waves x 16 keys = 64 keys, three workgroups
+// resident per CU at D 128; pass 2: 4 waves x 32 q rows = 128, two resident)
+// and streams the other index in steps of 32. Several independent workgroups
+// per CU are what hides a workgroup's load wait and barrier.
 //   - the first two products put the OUTER index on the MFMA lane
 //     (pass 1: S = Q K^T, dP = dO V^T with the key on the lane; pass 2:
 //     S^T = K Q^T, dP^T = V dO^T with the q row on the lane). A pair of
@@ -34,7 +36,11 @@
 //   - steps with nothing to mask (all rows in range, below the causal
 //     diagonal, no kv mask) skip the predicate; steps fully above the
 //     diagonal skip the math.
-//   - pass 2 launches the causal-heaviest q blocks first.
+//   - pass 2 launches the causal-heaviest q blocks first. Pass 1 is a 1-D
+//     grid whose workgroup id is mapped to (key block, b * Hk + kv head) by
+//     flash_bwd_wgmap.h: the key blocks of one (b, kv head), which all
+//     stream the same Q / dO, get ids of one residue mod 8 and so share an
+//     XCD and its L2, heaviest first; every XCD gets the same work.
 // Results are written transposed from the accumulators: 4 consecutive d per
 // lane, one 8-byte store.
 //
@@ -49,6 +55,7 @@
 
 #include "common.h"
 #include "flash_bwd_layout.h"
+#include "flash_bwd_wgmap.h"
 #include "lds_tr_read.h"
 
 using bf16x8_t = __attribute__((ext_vector_type(8))) short;
@@ -60,12 +67,20 @@ using u32x2_t = __attribute__((ext_vector_type(2))) unsigned int;
 
 namespace bwd {
 
-constexpr int BR = 128;   // outer rows per workgroup
+constexpr int BR = 128;   // q rows per workgroup, pass 2; padding of Sp
 constexpr int WR = 32;    // q rows per wave, pass 2 (4 waves)
-// 16-key tiles per wave, pass 1 (8 / KTW1 waves). 2 needs 128 + 64 registers
-// for dK^T, dV^T and the K/V fragments alone: at D 128 it spills under a
-// 256-register budget and was slower at one wave per SIMD than 1 at two.
+// 16-key tiles per wave, pass 1. 2 needs 128 + 64 registers for dK^T, dV^T
+// and the K/V fragments alone: at D 128 it spills under a 256-register budget
+// and was slower at one wave per SIMD than 1 at two.
 constexpr int KTW1 = 1;
+// Waves per workgroup, pass 1: 4 waves = 64 keys, so that three (D 128: 161
+// registers, 33 KB of LDS each) or four (D 64) independent workgroups share a
+// CU and one's load wait and barrier run under the others' MFMAs. 8 waves
+// (one workgroup per CU) and 2 (178 + 64 registers at D 128: two waves per
+// SIMD, not three) were measured slower: profiles/README.md.
+constexpr int NW1 = 4;
+constexpr int BRK1 = 16 * KTW1 * NW1;  // keys per workgroup, pass 1
+static_assert(BR % BRK1 == 0, "Sp covers every pass 1 workgroup's q steps");
 constexpr int TS = 32;    // streamed rows per step
 static_assert(TS == bwd_layout::TS, "the image layout is for 32-row steps");
 constexpr int PT = 64;    // rows per pre-pass tile
@@ -201,14 +216,15 @@ DEV_INLINE void unrotate_row(f32x4_t* acc /* [NDT] tiles, STRIDE apart */,
 }
 
 // ---------------------------------------------------------------------------
-// PASS 1: kv-outer. Block: 8 / KTW waves x 16 * KTW keys = 128 keys; q steps
-// of 32 over every q head of the group. Accumulates dK^T, dV^T (d on the
-// register row, key on the lane).
+// PASS 1: kv-outer. Block: NW waves x 16 * KTW keys = BRK keys; q steps of 32
+// over every q head of the group. Accumulates dK^T, dV^T (d on the register
+// row, key on the lane). A key's accumulators see the same steps in the same
+// order whatever NW is, so dk and dv do not depend on it.
 // ---------------------------------------------------------------------------
 // ROPE: q and k are the rotated tensors forward attended over; dk is returned
 // with respect to the un-rotated k (rope_cos/rope_sin: fp32 [>=S, DH/2]).
-template <int DH, int KTW, bool ROPE>
-__launch_bounds__(512 / KTW, 1)
+template <int DH, int KTW, int NW, bool ROPE>
+__launch_bounds__(64 * NW, DH == 128 ? 3 : 4)
 __global__ void flash_bwd_dkv_kernel(
     const short* __restrict__ q,     // [B,S,Hq,D]
     const short* __restrict__ k,     // [B,S,Hk,D]
@@ -226,8 +242,8 @@ __global__ void flash_bwd_dkv_kernel(
   constexpr int NDT = DH / 16;        // d-tiles of dK^T / dV^T
   constexpr int IMG = TS * DH * 2;    // bytes per image
   constexpr int SPI = DH / 16;        // 1 KiB segments per image
-  constexpr int NW = 8 / KTW;         // waves
   constexpr int WRK = 16 * KTW;       // keys per wave
+  constexpr int BRK = WRK * NW;       // keys per workgroup
   constexpr int LD_OFF = 2 * IMG;     // lse[32], Drow[32]
   constexpr int BUF = LD_OFF + 256;
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
@@ -240,11 +256,15 @@ __global__ void flash_bwd_dkv_kernel(
   const int l15 = lane & 15;
   const int l4 = lane >> 4;
 
-  const int bh = blockIdx.y;            // over B * Hk (kv heads)
+  // 1-D grid of ceil(S / BRK) * B * Hk workgroups: a (b, kv head)'s key
+  // blocks share an XCD, heaviest (causal: block 0) first
+  const bwd_wgmap::WgIndex wg =
+      bwd_wgmap::wg_index(blockIdx.x, (S + BRK - 1) / BRK, B * Hk);
+  const int bh = wg.bh;                 // over B * Hk (kv heads)
   const int b = bh / Hk;
   const int hk = bh % Hk;
   const int G = Hq / Hk;
-  const int kv_base = blockIdx.x * BR;  // causal: heaviest block first
+  const int kv_base = wg.kb * BRK;
   const int wk = kv_base + wave * WRK;
 
   const long long qrs = (long long)Hq * DH;
@@ -296,17 +316,23 @@ __global__ void flash_bwd_dkv_kernel(
   const int nq = (S - q_start + TS - 1) / TS;
   const int total = G * nq;
 
-  static_assert(SPI <= NW, "one image segment per wave at the most");
-  // one step's loads: the Q and dO images, lse/Drow
+  static_assert(NW >= SPI || SPI % NW == 0,
+                "the waves share an image's segments evenly");
+  // one step's loads: the Q and dO images, lse/Drow. Wave w issues segments
+  // w, w + NW, .. of each image.
   auto issue = [&](int g, int qb, int bufi) {
     const int h = hk * G + g;
     char* buf = smem + bufi * BUF;
     const short* qp = q + ((long long)b * S) * qrs + h * DH;
     const short* dop = dout + ((long long)b * S) * qrs + h * DH;
     const long long roff = ((long long)b * Hq + h) * Sp;
-    if (wave < SPI) {
-      issue_rm<DH>(qp, qrs, qb, S, buf, wave, lane);
-      issue_rm<DH>(dop, qrs, qb, S, buf + IMG, wave, lane);
+#pragma unroll
+    for (int i = 0; i < (SPI + NW - 1) / NW; ++i) {
+      const int sseg = wave + i * NW;
+      if (sseg < SPI) {
+        issue_rm<DH>(qp, qrs, qb, S, buf, sseg, lane);
+        issue_rm<DH>(dop, qrs, qb, S, buf + IMG, sseg, lane);
+      }
     }
     if (wave == 0) {
       const float* s = (lane < 32 ? lseP : drowP) + roff + qb + (lane & 31);
@@ -680,12 +706,15 @@ static void launch_bwd(at::Tensor& q, at::Tensor& k, at::Tensor& v,
                      lse.data_ptr<float>(), drow.data_ptr<float>(),
                      lseP.data_ptr<float>(), B, S, Sp, Hq);
   HIP_CHECK_KERNEL();
-  dim3 grid1(Sp / bwd::BR, B * Hk);
-  hipLaunchKernelGGL((bwd::flash_bwd_dkv_kernel<DH, bwd::KTW1, ROPE>), grid1,
-                     dim3(512 / bwd::KTW1), 0, stream.stream(), sp(q), sp(k),
-                     sp(v), sp(dout), lseP.data_ptr<float>(),
-                     drow.data_ptr<float>(), mp, spm(dk), spm(dv), cosp, sinp,
-                     B, S, Sp, Hq, Hk, scale, causal);
+  // 1-D: the kernel maps the workgroup id to (key block, b * Hk + kv head)
+  // with bwd_wgmap::wg_index, so the grid is exactly their product
+  const int nkb1 = (S + bwd::BRK1 - 1) / bwd::BRK1;
+  dim3 grid1(nkb1 * B * Hk);
+  hipLaunchKernelGGL(
+      (bwd::flash_bwd_dkv_kernel<DH, bwd::KTW1, bwd::NW1, ROPE>), grid1,
+      dim3(64 * bwd::NW1), 0, stream.stream(), sp(q), sp(k), sp(v), sp(dout),
+      lseP.data_ptr<float>(), drow.data_ptr<float>(), mp, spm(dk), spm(dv),
+      cosp, sinp, B, S, Sp, Hq, Hk, scale, causal);
   HIP_CHECK_KERNEL();
   dim3 grid2(Sp / bwd::BR, B * Hq);
   hipLaunchKernelGGL((bwd::flash_bwd_dq_kernel<DH, ROPE>), grid2, dim3(256), 0,
