@@ -16,6 +16,7 @@
 #include <torch/extension.h>
 
 #include "common.h"
+#include "flash_bwd_wgmap.h"
 #include "flash_fwd_layout.h"
 #include "lds_tr_read.h"
 
@@ -39,6 +40,16 @@ using bf16x8_t = __attribute__((ext_vector_type(8))) short;
 //     its bank-conflict argument (both reads degree 1), is flash_fwd_layout.h.
 //   - image rows past S-1 repeat row S-1 (nothing outside q, k, v is read);
 //     their score is -inf, so their P is exactly 0.
+//   - causal diagonal at wave granularity: in a block's last 4 key tiles,
+//     wave w needs only w/2 + 1 of them. A wave skips the products, softmax
+//     and V reads of a tile that lies wholly above its 32 rows' diagonal
+//     (12 of 32 wave-tiles) but still issues its share of the next tile's
+//     DMA and meets the barrier; the skipped tile would have added +0.
+//   - 1-D grid; the workgroup id is mapped to (q block, b * Hq + q head) by
+//     flash_bwd_wgmap.h: the q blocks of one (b, q head) get ids of one
+//     residue mod 8 and so share an XCD, heaviest (the last) first, and
+//     every XCD gets the same causal work. The plain (q block, bh) grid gave
+//     the heaviest XCD 41 % more key tiles than the mean at 16 q blocks.
 // C/D layout (32x32x16): col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5).
 // A/B operand: row(col)=lane&31, k=(lane>>5)*8+j.
 // ===========================================================================
@@ -112,8 +123,12 @@ __global__ void flash_fwd_v6_kernel(
   constexpr int NQF = DH / 16;   // Q k-slices
   constexpr int NOT = DH / 32;   // O^T d m-tiles
 
-  const int qtile = blockIdx.x;
-  const int bh = blockIdx.y;
+  // 1-D grid of ceil(S / QT5) * B * Hq workgroups: the q blocks of a (b, q
+  // head) share an XCD, heaviest (causal: the last block) first
+  const bwd_wgmap::QIndex wg =
+      bwd_wgmap::q_index(blockIdx.x, (S + QT5 - 1) / QT5, B * Hq);
+  const int qtile = wg.qb;
+  const int bh = wg.bh;
   const int b = bh / Hq;
   const int h = bh % Hq;
   const int hk = h / (Hq / Hk);
@@ -192,6 +207,11 @@ __global__ void flash_fwd_v6_kernel(
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (t + 1 < n_tiles) issue_tile(t + 1);  // lands in the other buffers
+    // Wave-uniform (EXEC stays full around the transposed reads): every score
+    // of this wave's 32 rows is above the causal diagonal, so every P would
+    // be exactly 0 and nothing would rescale. The wave has issued its share
+    // of the next tile and meets the next barrier.
+    if (causal && kvbase > wave_q + QB5 - 1) continue;
     const char* kimg = smem + (t & 1) * IMG;
     const unsigned vimg = smem_a + (2 + (t & 1)) * IMG;
 
@@ -392,7 +412,12 @@ std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k,
   auto out = at::empty_like(q);
   auto lse = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
   auto stream = c10::hip::getCurrentHIPStream();
-  dim3 grid((S + QT5 - 1) / QT5, B * Hq);
+  // 1-D: the kernel maps the workgroup id to (q block, b * Hq + q head) with
+  // bwd_wgmap::q_index, so the grid is exactly their product
+  const long long nwg = (long long)((S + QT5 - 1) / QT5) * B * Hq;
+  TORCH_CHECK(nwg * 512 <= UINT32_MAX, "flash_attn_fwd: ", nwg,
+              " workgroups of 512 threads exceed the 1-D grid limit");
+  dim3 grid((unsigned)nwg);
   if (D == 128) {
     hipLaunchKernelGGL(flash_fwd_v6_kernel<128>, grid, dim3(512), 0,
                        stream.stream(),

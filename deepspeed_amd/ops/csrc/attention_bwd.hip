@@ -36,11 +36,12 @@
 //   - steps with nothing to mask (all rows in range, below the causal
 //     diagonal, no kv mask) skip the predicate; steps fully above the
 //     diagonal skip the math.
-//   - pass 2 launches the causal-heaviest q blocks first. Pass 1 is a 1-D
-//     grid whose workgroup id is mapped to (key block, b * Hk + kv head) by
-//     flash_bwd_wgmap.h: the key blocks of one (b, kv head), which all
-//     stream the same Q / dO, get ids of one residue mod 8 and so share an
-//     XCD and its L2, heaviest first; every XCD gets the same work.
+//   - both passes are 1-D grids whose workgroup id is mapped by
+//     flash_bwd_wgmap.h, pass 1 to (key block, b * Hk + kv head), pass 2 to
+//     (q block, b * Hq + q head): the blocks of one bh, which all stream the
+//     same rows (pass 1: Q / dO; pass 2: K / V), get ids of one residue mod 8
+//     and so share an XCD and its L2, causal-heaviest first (key block 0; the
+//     last q block); every XCD gets the same work.
 // Results are written transposed from the accumulators: 4 consecutive d per
 // lane, one 8-byte store.
 //
@@ -511,9 +512,12 @@ __global__ void flash_bwd_dq_kernel(
   const int l15 = lane & 15;
   const int l4 = lane >> 4;
 
-  // causal: the last q block has the most kv steps; launch it first
-  const int qtile = gridDim.x - 1 - blockIdx.x;
-  const int bh = blockIdx.y;
+  // 1-D grid of Sp / BR * B * Hq workgroups: the q blocks of a (b, q head)
+  // share an XCD, heaviest (causal: the last block, most kv steps) first
+  const bwd_wgmap::QIndex wg =
+      bwd_wgmap::q_index(blockIdx.x, Sp / BR, B * Hq);
+  const int qtile = wg.qb;
+  const int bh = wg.bh;
   const int b = bh / Hq;
   const int h = bh % Hq;
   const int hk = h / (Hq / Hk);
@@ -716,7 +720,11 @@ static void launch_bwd(at::Tensor& q, at::Tensor& k, at::Tensor& v,
       lseP.data_ptr<float>(), drow.data_ptr<float>(), mp, spm(dk), spm(dv),
       cosp, sinp, B, S, Sp, Hq, Hk, scale, causal);
   HIP_CHECK_KERNEL();
-  dim3 grid2(Sp / bwd::BR, B * Hq);
+  // 1-D as well: (q block, b * Hq + q head) by bwd_wgmap::q_index
+  const long long nwg2 = (long long)(Sp / bwd::BR) * B * Hq;
+  TORCH_CHECK(nwg2 * 256 <= UINT32_MAX, "flash_attn_bwd: ", nwg2,
+              " workgroups of 256 threads exceed the 1-D grid limit");
+  dim3 grid2((unsigned)nwg2);
   hipLaunchKernelGGL((bwd::flash_bwd_dq_kernel<DH, ROPE>), grid2, dim3(256), 0,
                      stream.stream(), sp(q), sp(k), sp(v), sp(dout),
                      lseP.data_ptr<float>(), drow.data_ptr<float>(), mp,

@@ -15,7 +15,8 @@ mask.
 Environment: AB_B (1), AB_S (4096), AB_D (128), AB_HQ (32), AB_HK (8),
 AB_CAUSAL (1), AB_ITERS (20, at least 20 are run), AB_BWD_ONLY (0: set to 1
 to skip the forward and SDPA timings), AB_FWD_ONLY (0: set to 1 to time
-`flash_attn_fwd` alone, min and median, and nothing else).
+`flash_attn_fwd` alone, min and median, and nothing else; with AB_BWD_ONLY=1
+as well, the forward alone and then the backward alone, in one process).
 """
 import math
 import os
@@ -77,7 +78,8 @@ def main():
         print(f"fwd only: min {t_min:8.3f} ms  median {t_med:8.3f} ms")
         print(f"fwd only: {2 * product / t_min / 1e9:7.1f} TF/s "
               f"(2 products), at min")
-        return
+        if not BWD_ONLY:
+            return
 
     with torch.no_grad():
         out, lse = ext.flash_attn_fwd(q, k, v, CAUSAL, scale)
