@@ -22,9 +22,30 @@ def _hf_rope_theta(hf_config):
     return float(getattr(hf_config, "rope_theta", 500000.0))
 
 
+def _hf_sliding_window(hf_config):
+    # Mistral / Mixtral / Qwen2 configs; Qwen2 carries the size even when its
+    # use_sliding_window switch is off
+    if getattr(hf_config, "use_sliding_window", True) is False:
+        return None
+    win = getattr(hf_config, "sliding_window", None)
+    if win is None:
+        return None
+    # Qwen2 windows only the layers from max_window_layers on; the native
+    # config has one window for all layers
+    first = getattr(hf_config, "max_window_layers", 0) or 0
+    if first >= hf_config.num_hidden_layers:
+        return None
+    if first > 0:
+        raise NotImplementedError(
+            f"sliding_window on layers {first}.. only (max_window_layers) is "
+            "not supported: LlamaConfig.sliding_window applies to every layer")
+    return int(win)
+
+
 def config_from_hf(hf_config):
     """Map a transformers LlamaConfig to the native LlamaConfig."""
     return LlamaConfig(
+        sliding_window=_hf_sliding_window(hf_config),
         hidden_size=hf_config.hidden_size,
         intermediate_size=hf_config.intermediate_size,
         num_hidden_layers=hf_config.num_hidden_layers,

@@ -5,6 +5,7 @@ fused cross-entropy; hipBLASLt GEMMs via F.linear). Used by bench.py for the
 BASELINE config "Llama-3 8B ZeRO-3 bf16".
 """
 from dataclasses import dataclass, field
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -30,6 +31,9 @@ class LlamaConfig:
     initializer_range: float = 0.02
     activation_checkpointing: bool = True
     attention_bias: bool = False  # Qwen2-style qkv bias
+    # Mistral-style sliding window: a token attends the last `sliding_window`
+    # tokens, itself included. None = the full causal triangle.
+    sliding_window: Optional[int] = None
 
     @property
     def head_dim(self):
@@ -96,6 +100,18 @@ class LlamaAttention(nn.Module):
         q = self.q_proj(x).view(B, S, -1, d)
         k = self.k_proj(x).view(B, S, -1, d)
         v = self.v_proj(x).view(B, S, -1, d)
+        # sliding window: passed to the flash kernels on the training path
+        # and the plain prefill; the paths that cannot honour it refuse
+        win = getattr(self.cfg, "sliding_window", None)
+        wkw = {} if win is None else {"window": win}
+        if win is not None and (getattr(kv_cache, "fuses_rope", False)
+                                or getattr(kv_cache, "ragged", None)
+                                is not None
+                                or getattr(kv_cache, "fused", None)
+                                is not None):
+            raise NotImplementedError(
+                "sliding_window is not supported by the ragged / fp8 slot-pool "
+                "attention kernels: they would attend the whole context")
         # RoPE uses the caller's cos/sin slice (seq-offset aware under SP)
         if getattr(kv_cache, "fuses_rope", False):
             # ragged serving step with fused_kv_append: RoPE of q and k, the
@@ -105,7 +121,8 @@ class LlamaAttention(nn.Module):
             if kv_cache is None and self._dist_attn is None:
                 # plain training path: RoPE of q and k in one launch, its
                 # backward inside the flash backward epilogues
-                o = rope_flash_attention(q, k, v, cos, sin, causal=True)
+                o = rope_flash_attention(q, k, v, cos, sin, causal=True,
+                                         **wkw)
                 if o is not None:
                     return self.o_proj(o.reshape(B, S, -1))
             q = apply_rope(q, cos, sin)
@@ -139,13 +156,23 @@ class LlamaAttention(nn.Module):
             else:
                 mask = getattr(kv_cache, "attn_mask", None)
                 causal = S > 1  # prefill is causal; decode sees all past
-                o = flash_attention(q, k, v,
-                                    causal=causal and mask is None,
-                                    attn_mask=mask)
+                if win is not None and k.shape[1] > win:
+                    # only a whole-sequence prefill is a band the kernels know
+                    if not (causal and mask is None and k.shape[1] == S):
+                        raise NotImplementedError(
+                            f"sliding_window={win}: decode or masked prefill "
+                            f"over a context of {k.shape[1]} tokens would "
+                            "attend past the window")
+                    o = flash_attention(q, k, v, causal=True, window=win)
+                else:
+                    o = flash_attention(q, k, v,
+                                        causal=causal and mask is None,
+                                        attn_mask=mask)
         elif self._dist_attn is not None:
-            o = self._dist_attn(q, k, v, causal=True)
+            # Ulysses: the local attention sees the full sequence
+            o = self._dist_attn(q, k, v, causal=True, **wkw)
         else:
-            o = flash_attention(q, k, v, causal=True)
+            o = flash_attention(q, k, v, causal=True, **wkw)
         return self.o_proj(o.reshape(B, S, -1))
 
 
@@ -194,6 +221,11 @@ def llama_decode_step(model, ids, caches, pos_idx, attn_mask, cos_t, sin_t):
     additive; cos_t/sin_t: full rope tables on device.
     """
     core = model.model
+    win = getattr(core.layers[0].self_attn.cfg, "sliding_window", None)
+    if win is not None and caches[0].max_seq > win:
+        raise NotImplementedError(
+            f"sliding_window={win}: StaticKVCache decode attends the whole "
+            f"cache (max_seq {caches[0].max_seq})")
     x = core.embed_tokens(ids)
     cos = cos_t.index_select(0, pos_idx)
     sin = sin_t.index_select(0, pos_idx)

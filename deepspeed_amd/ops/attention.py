@@ -14,10 +14,15 @@ over the GQA group in-kernel. Faster than the SDPA backward at the
 training shape; measurements in profiles/README.md.
 Set DSAMD_FLASH=0 to fall back to torch SDPA; a chunked-GEMM backward
 (DSAMD_FLASH_BWD=0) remains as a reference implementation.
+Banded causal masks (window=, segment_ids=: sliding window and packed
+documents) are one restriction, row i sees keys kv_lo[i] .. i with kv_lo
+non-decreasing, and run in the BAND variants of the same three kernels, which
+start each block at its band instead of key 0 / end it before row S.
 
 Parity role: reference inference/v2 blocked flash kernels + training
 softmax/attention kernels (csrc/transformer/softmax_kernels.cu).
 """
+import functools
 import math
 import os
 
@@ -29,32 +34,36 @@ from .loader import get_ext
 
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale, kvmask=None):
+    def forward(ctx, q, k, v, causal, scale, kvmask=None, kv_lo=None,
+                q_hi=None):
         ext = get_ext(required=True)
-        out, lse = ext.flash_attn_fwd(q, k, v, causal, scale, kvmask)
+        band = () if kv_lo is None else (kv_lo, q_hi)
+        out, lse = ext.flash_attn_fwd(q, k, v, causal, scale, kvmask, *band)
         ctx.save_for_backward(q, k, v, out, lse,
                               kvmask if kvmask is not None
-                              else torch.empty(0))
+                              else torch.empty(0), *band)
         ctx.causal = causal
         ctx.scale = scale
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, out, lse, kvmask = ctx.saved_tensors
+        q, k, v, out, lse, kvmask, *band = ctx.saved_tensors
         if kvmask.numel() == 0:
             kvmask = None
         dq, dk, dv = _flash_backward(q, k, v, out, lse, kvmask, ctx.causal,
-                                     ctx.scale, dout)
-        return dq, dk, dv, None, None, None
+                                     ctx.scale, dout, band=band)
+        return dq, dk, dv, None, None, None, None, None
 
 
 def _flash_backward(q, k, v, out, lse, kvmask, causal, scale, dout,
-                    cos=None, sin=None):
+                    cos=None, sin=None, band=()):
     """dq, dk, dv of flash attention from the saved LSE. With cos/sin, q and
     k are the RoPE-rotated tensors and dq, dk are returned with respect to
     the un-rotated ones: the HIP kernels un-rotate in their epilogues, the
-    reference route (DSAMD_FLASH_BWD=0) runs the rope kernel afterwards."""
+    reference route (DSAMD_FLASH_BWD=0) runs the rope kernel afterwards.
+    band: () or (kv_lo, q_hi) of _band_bounds; HIP kernels only (a banded
+    call never reaches the reference route)."""
     B, S, Hq, D = q.shape
     Hk = k.shape[2]
     G = Hq // Hk
@@ -63,8 +72,9 @@ def _flash_backward(q, k, v, out, lse, kvmask, causal, scale, dout,
         ext = get_ext(required=True)
         dq, dk, dv = ext.flash_attn_bwd(
             q, k, v, dout.contiguous(), out, lse, causal, scale, kvmask,
-            cos, sin)
+            cos, sin, *band)
         return dq, dk, dv
+    assert not band, "the chunked-GEMM reference backward has no band"
 
     # head-major views [B,H,S,D]
     qh = q.permute(0, 2, 1, 3)
@@ -130,22 +140,24 @@ class _RopeFlashAttnFn(torch.autograd.Function):
     no standalone rope kernel runs over dq and dk."""
 
     @staticmethod
-    def forward(ctx, q, k, v, cos, sin, causal, scale):
+    def forward(ctx, q, k, v, cos, sin, causal, scale, kv_lo=None,
+                q_hi=None):
         ext = get_ext(required=True)
         qr, kr = ext.rope_qk(q.contiguous(), k.contiguous(), cos, sin)
         v = v.contiguous()
-        out, lse = ext.flash_attn_fwd(qr, kr, v, causal, scale, None)
-        ctx.save_for_backward(qr, kr, v, out, lse, cos, sin)
+        band = () if kv_lo is None else (kv_lo, q_hi)
+        out, lse = ext.flash_attn_fwd(qr, kr, v, causal, scale, None, *band)
+        ctx.save_for_backward(qr, kr, v, out, lse, cos, sin, *band)
         ctx.causal = causal
         ctx.scale = scale
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        qr, kr, v, out, lse, cos, sin = ctx.saved_tensors
+        qr, kr, v, out, lse, cos, sin, *band = ctx.saved_tensors
         dq, dk, dv = _flash_backward(qr, kr, v, out, lse, None, ctx.causal,
-                                     ctx.scale, dout, cos, sin)
-        return dq, dk, dv, None, None, None, None
+                                     ctx.scale, dout, cos, sin, band=band)
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 # Training default: the in-tree HIP kernels (fwd v5 beats SDPA; bwd beats
@@ -175,11 +187,84 @@ def _as_kv_padding_mask(attn_mask, B, Sk):
     return m.contiguous().float()
 
 
-def rope_flash_attention(q, k, v, cos, sin, causal=True):
+def _band_bounds(B, S, window, segment_ids, device):
+    """The banded causal mask "row i sees keys kv_lo[i] .. i" as two
+    contiguous int32 [B,S] tensors (kv_lo, q_hi), or None when the band is the
+    whole causal triangle. kv_lo[b,i] is the first admissible key of row i:
+    max(0, i - window + 1) under a window, the first index of i's segment
+    under segment_ids, the larger of the two under both. It is non-decreasing
+    in i, so the rows that admit key j are exactly j .. q_hi[b,j] - 1 with
+    q_hi[b,j] the number of rows whose kv_lo is <= j: q_hi is computed from
+    kv_lo, never from the arguments, so the two cannot disagree.
+    A window alone gives the same bounds to every layer and step of a model:
+    those are computed once per (B, S, window, device) and kept. With
+    segment_ids they are rebuilt on every call, which also reads two flags
+    back from the device."""
+    if window is not None and window < 1:
+        raise ValueError(f"window must be >= 1, got {window}")
+    if segment_ids is None:
+        return _window_bounds(B, S, window, torch.device(device))
+    return _compute_band_bounds(B, S, window, segment_ids, device)
+
+
+@functools.lru_cache(maxsize=16)
+def _window_bounds(B, S, window, device):
+    return _compute_band_bounds(B, S, window, None, device)
+
+
+def _compute_band_bounds(B, S, window, segment_ids, device):
+    rows = torch.arange(S, device=device)
+    if window is not None and window < S:
+        lo = (rows - (window - 1)).clamp_(min=0).expand(B, S)
+    elif segment_ids is None:
+        return None
+    else:
+        lo = torch.zeros(B, S, dtype=torch.int64, device=device)
+    if segment_ids is not None:
+        if segment_ids.shape != (B, S) or segment_ids.is_floating_point():
+            raise ValueError("segment_ids must be an integer [B,S] tensor")
+        seg = segment_ids.to(device=device, dtype=torch.int64).contiguous()
+        # first index of each row's segment; one host read decides both
+        # whether the ids are valid and whether any band is left
+        lo = torch.maximum(lo, torch.searchsorted(seg, seg))
+        decreasing, banded = torch.stack(
+            [(seg[:, 1:] < seg[:, :-1]).any(), (lo > 0).any()]).tolist()
+        if decreasing:
+            raise ValueError("segment_ids must be non-decreasing along S")
+        if not banded:
+            return None
+    lo = lo.contiguous()
+    q_hi = torch.searchsorted(lo, rows.expand(B, S).contiguous(), right=True)
+    return lo.int(), q_hi.int()
+
+
+def _band_mask(kv_lo):
+    """Boolean [B,1,S,S] admissibility of the band, for the SDPA fallback."""
+    S = kv_lo.shape[1]
+    idx = torch.arange(S, device=kv_lo.device)
+    return ((idx.view(1, 1, S) >= kv_lo.unsqueeze(-1)) &
+            (idx.view(1, 1, S) <= idx.view(1, S, 1))).unsqueeze(1)
+
+
+def _check_band_args(window, segment_ids, causal, attn_mask):
+    if window is None and segment_ids is None:
+        return False
+    if not causal:
+        raise ValueError("window / segment_ids require causal=True")
+    if attn_mask is not None:
+        raise ValueError("window / segment_ids cannot be combined with "
+                         "attn_mask")
+    return True
+
+
+def rope_flash_attention(q, k, v, cos, sin, causal=True, window=None,
+                         segment_ids=None):
     """flash_attention(rope(q), rope(k), v) for the plain training path, or
     None when that path does not apply (CPU, not bf16, per-row positions,
     DSAMD_FLASH=0 or DSAMD_FLASH_BWD=0): the caller then takes the unfused
-    apply_rope + flash_attention route."""
+    apply_rope + flash_attention route. window / segment_ids: as in
+    flash_attention."""
+    banded = _check_band_args(window, segment_ids, causal, None)
     D = q.shape[-1]
     if not (_USE_HIP_FLASH and q.is_cuda and q.dtype == torch.bfloat16
             and D in (64, 128) and q.shape[1] == k.shape[1]
@@ -192,19 +277,48 @@ def rope_flash_attention(q, k, v, cos, sin, causal=True):
     sin = sin.float().contiguous()
     if cos.data_ptr() % 16 or sin.data_ptr() % 16:
         return None
+    band = _band_bounds(q.shape[0], q.shape[1], window, segment_ids,
+                        q.device) if banded else None
+    if band is not None:
+        return _RopeFlashAttnFn.apply(q, k, v, cos, sin, causal,
+                                      1.0 / math.sqrt(D), *band)
     return _RopeFlashAttnFn.apply(q, k, v, cos, sin, causal,
                                   1.0 / math.sqrt(D))
 
 
-def flash_attention(q, k, v, causal=True, attn_mask=None):
+def flash_attention(q, k, v, causal=True, attn_mask=None, window=None,
+                    segment_ids=None):
     """q [B,S,Hq,D], k/v [B,S,Hkv,D] -> [B,S,Hq,D]. GQA-aware.
 
     attn_mask: optional additive float mask. KV-padding-shaped masks
     ([B,1,1,Sk] etc., the BERT case) run in the HIP kernel; arbitrary
-    [B,Hq,Sq,Sk] masks route through SDPA."""
+    [B,Hq,Sq,Sk] masks route through SDPA.
+    window: row i attends keys max(0, i - window + 1) .. i (sliding window of
+    `window` keys, itself included). segment_ids: integer [B,S],
+    non-decreasing along S (packed documents); row i attends only keys of its
+    own segment. Both need causal=True and no attn_mask, may be combined (the
+    band is their intersection) and run in the HIP kernels' BAND variants;
+    where those do not apply (CPU, not bf16, other head dims, DSAMD_FLASH=0,
+    DSAMD_FLASH_BWD=0) the band goes to SDPA as a boolean mask."""
     scale = 1.0 / math.sqrt(q.shape[-1])
     hip_ok = _USE_HIP_FLASH and q.is_cuda and q.dtype == torch.bfloat16 \
         and q.shape[-1] in (64, 128) and q.shape[1] == k.shape[1]
+    if _check_band_args(window, segment_ids, causal, attn_mask):
+        if q.shape[1] != k.shape[1]:
+            raise ValueError("window / segment_ids need q and k of one length, "
+                             f"got {q.shape[1]} and {k.shape[1]}")
+        band = _band_bounds(q.shape[0], q.shape[1], window, segment_ids,
+                            q.device)
+        if band is not None:
+            if hip_ok and os.environ.get("DSAMD_FLASH_BWD", "1") == "1":
+                return _FlashAttnFn.apply(q.contiguous(), k.contiguous(),
+                                          v.contiguous(), True, scale, None,
+                                          *band)
+            out = F.scaled_dot_product_attention(
+                q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
+                attn_mask=_band_mask(band[0]), is_causal=False,
+                enable_gqa=(k.shape[2] != q.shape[2]))
+            return out.transpose(1, 2)
     if attn_mask is not None:
         kvm = _as_kv_padding_mask(attn_mask, q.shape[0], k.shape[1]) \
             if hip_ok else None

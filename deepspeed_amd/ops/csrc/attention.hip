@@ -50,6 +50,23 @@ using bf16x8_t = __attribute__((ext_vector_type(8))) short;
 //     residue mod 8 and so share an XCD, heaviest (the last) first, and
 //     every XCD gets the same causal work. The plain (q block, bh) grid gave
 //     the heaviest XCD 41 % more key tiles than the mean at 16 q blocks.
+//   - BAND (template parameter; sliding window and packed documents): row i
+//     sees keys kv_lo[i] .. i, kv_lo a non-decreasing int32 [B,S] array. The
+//     q row is on the lane, so the band costs one register, the lane's own
+//     kv_lo, and the predicate gains `gkv >= lo`. Because kv_lo does not
+//     decrease, the block's first row has the block's smallest bound: the
+//     tile loop and its DMA prologue start at tile kv_lo[qbase] / 64, which
+//     is where the band variant does less work than the triangle. Within the
+//     block a wave skips a tile that ends at or before kv_lo of ITS first
+//     row, exactly as it skips one above its diagonal (it still issues its
+//     DMA share and meets the barrier), and a tile takes the cmp-free path
+//     only if it also starts at or after kv_lo of the wave's last in-range
+//     row, the wave's largest bound. The three bounds are scalar, so EXEC
+//     stays full. Every value read from kv_lo is clamped into [0, S] and the
+//     first tile to the last causal tile: a wrong array mis-masks but reads
+//     nothing new. With kv_lo = 0 the variant visits the same tiles in the
+//     same order as the plain kernel and is bit-identical to it. BAND = false
+//     compiles to the code it was before the parameter existed.
 // C/D layout (32x32x16): col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5).
 // A/B operand: row(col)=lane&31, k=(lane>>5)*8+j.
 // ===========================================================================
@@ -97,7 +114,9 @@ DEV_INLINE void issue_v_dtile(tr_frag (&f)[4], unsigned base) {
 
 // kvmask: optional [B,S] additive float mask over kv columns (padding
 // masks, ALiBi-free BERT-class workloads); nullptr = none.
-template <int DH>
+// BAND: causal is taken as given, kvmask as absent, and kv_lo ([B,S] int32,
+// non-decreasing along S) is the first admissible key of each q row.
+template <int DH, bool BAND>
 __launch_bounds__(512, 2)
 __global__ void flash_fwd_v6_kernel(
     const short* __restrict__ q,  // [B,S,Hq,D]
@@ -106,7 +125,8 @@ __global__ void flash_fwd_v6_kernel(
     short* __restrict__ out,      // [B,S,Hq,D]
     float* __restrict__ lse_out,  // [B,Hq,S]
     const float* __restrict__ kvmask,  // [B,S] or null
-    int B, int S, int Hq, int Hk, float scale, int causal) {
+    int B, int S, int Hq, int Hk, float scale, int causal,
+    const int* __restrict__ kv_lo) {  // BAND only, else null
   // K and V double-buffered, one array: [K 0][K 1][V 0][V 1], each a
   // row-major image of flash_fwd_layout.h. Tile t+1's global_load_lds issue
   // before tile t's compute.
@@ -141,7 +161,28 @@ __global__ void flash_fwd_v6_kernel(
   const short* qp = q + ((long long)b * S) * qrs + h * DH;
   const short* kp = k + ((long long)b * S) * kvrs + hk * DH;
   const short* vp = v + ((long long)b * S) * kvrs + hk * DH;
-  const float* mp = kvmask ? kvmask + (long long)b * S : nullptr;
+  const float* mp = (!BAND && kvmask) ? kvmask + (long long)b * S : nullptr;
+
+  // ---- BAND: the lane's first key, the block's and the wave's bounds ------
+  // Every value is clamped into [0, S]: a wrong array can mis-mask but the
+  // tile range below stays inside the causal one.
+  int lo = 0;         // first admissible key of this lane's row
+  int t_first = 0;    // first key tile of the block
+  int wlo_first = 0;  // kv_lo of the wave's first row: tiles below it skip
+  int wlo_last = 0;   // kv_lo of its last in-range row: tiles from it on need
+                      // no lower predicate
+  if constexpr (BAND) {
+    causal = 1;
+    const int* lop = kv_lo + (long long)b * S;
+    lo = band_clamp(lop[min(my_q, S - 1)], S);
+    // scalar (block / wave uniform addresses), so the branches on them are
+    // scalar too and EXEC stays full around the transposed reads
+    t_first = __builtin_amdgcn_readfirstlane(band_clamp(lop[qbase], S)) / KT5;
+    wlo_first = __builtin_amdgcn_readfirstlane(
+        band_clamp(lop[min(wave_q, S - 1)], S));
+    wlo_last = __builtin_amdgcn_readfirstlane(
+        band_clamp(lop[min(wave_q + QB5 - 1, S - 1)], S));
+  }
 
   // ---- Q fragments: qfrag[ks] = Q[my_q][16*ks + hi*8 .. +7] -------------
   bf16x8_t qfrag[NQF];
@@ -196,9 +237,13 @@ __global__ void flash_fwd_v6_kernel(
   };
 
   const unsigned smem_a = lds_addr(smem);
-  issue_tile(0);
+  // BAND: kv_lo is non-decreasing, so no row of the block admits a key below
+  // kv_lo[qbase]: the loop and the prologue start at that key's tile (at most
+  // the last tile, whatever the array holds)
+  const int t0 = BAND ? min(t_first, n_tiles - 1) : 0;
+  issue_tile(t0);
 
-  for (int t = 0; t < n_tiles; ++t) {
+  for (int t = t0; t < n_tiles; ++t) {
     const int kvbase = t * KT5;
     // This tile's loads (the only ones in flight) have landed; after the
     // barrier every wave is also done reading the other buffers. The bare
@@ -212,6 +257,9 @@ __global__ void flash_fwd_v6_kernel(
     // be exactly 0 and nothing would rescale. The wave has issued its share
     // of the next tile and meets the next barrier.
     if (causal && kvbase > wave_q + QB5 - 1) continue;
+    // BAND: the same below the band. The wave's first row has its smallest
+    // kv_lo, so a tile that ends at or before it holds no admissible key.
+    if (BAND && kvbase + KT5 <= wlo_first) continue;
     const char* kimg = smem + (t & 1) * IMG;
     const unsigned vimg = smem_a + (2 + (t & 1)) * IMG;
 
@@ -239,8 +287,11 @@ __global__ void flash_fwd_v6_kernel(
 
     // ---- online softmax (lane-local q row) ------------------------------
     // btile is wave-uniform: interior tiles take the cmp-free path
+    // (BAND: the wave's last in-range row has its largest kv_lo; a tile that
+    // starts at or after it is inside every row's band)
     const bool btile = (causal && (kvbase + KT5 > qbase)) ||
-                       (kvbase + KT5 > S) || mp != nullptr;
+                       (kvbase + KT5 > S) || mp != nullptr ||
+                       (BAND && kvbase < wlo_last);
     float tmax = -INFINITY;
     if (btile) {
 #pragma unroll
@@ -250,7 +301,8 @@ __global__ void flash_fwd_v6_kernel(
           float sv = st[mt][r] * sc2;
           int gkv = kvbase + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hi;
           if (mp && gkv < S) sv += mp[gkv] * 1.44269504f;
-          if ((causal && gkv > my_q) || gkv >= S) sv = -INFINITY;
+          if ((causal && gkv > my_q) || gkv >= S || (BAND && gkv < lo))
+            sv = -INFINITY;
           st[mt][r] = sv;
           tmax = fmaxf(tmax, sv);
         }
@@ -365,6 +417,43 @@ __global__ void flash_fwd_v6_kernel(
   }
 }
 
+// One launch, head dimension chosen at run time; lop null unless BAND.
+template <bool BAND>
+static void flash_fwd_launch(int D, dim3 grid, hipStream_t stream,
+                             const void* q, const void* k, const void* v,
+                             void* out, float* lse, const float* mp, int B,
+                             int S, int Hq, int Hk, float scale, int causal,
+                             const int* lop) {
+  auto kern = D == 128 ? flash_fwd_v6_kernel<128, BAND>
+                       : flash_fwd_v6_kernel<64, BAND>;
+  hipLaunchKernelGGL(kern, grid, dim3(512), 0, stream,
+                     static_cast<const short*>(q), static_cast<const short*>(k),
+                     static_cast<const short*>(v), static_cast<short*>(out),
+                     lse, mp, B, S, Hq, Hk, scale, causal, lop);
+}
+
+// The BAND instantiations live in a translation unit of their own,
+// attention_band.hip, which includes this file with DSAMD_FLASH_BAND_TU set
+// and is built without packed fp32 instructions (ops/build.py,
+// NO_PACKED_FP32, has the reason); this unit keeps the plain instantiations
+// and the build they were validated with.
+void flash_fwd_band_launch(int D, dim3 grid, hipStream_t stream,
+                           const void* q, const void* k, const void* v,
+                           void* out, float* lse, int B, int S, int Hq,
+                           int Hk, float scale, const int* kv_lo);
+
+#ifdef DSAMD_FLASH_BAND_TU
+
+void flash_fwd_band_launch(int D, dim3 grid, hipStream_t stream,
+                           const void* q, const void* k, const void* v,
+                           void* out, float* lse, int B, int S, int Hq,
+                           int Hk, float scale, const int* kv_lo) {
+  flash_fwd_launch<true>(D, grid, stream, q, k, v, out, lse, nullptr, B, S,
+                         Hq, Hk, scale, 1, kv_lo);
+}
+
+#else
+
 // Shared host-side contract of flash_attn_fwd / flash_attn_bwd: the kernels
 // index k and v with q's B and S and reinterpret every pointer as bf16.
 void flash_check_qkv(const at::Tensor& q, const at::Tensor& k,
@@ -398,14 +487,42 @@ const float* flash_check_kvmask(const c10::optional<at::Tensor>& kvmask,
   return kvmask->data_ptr<float>();
 }
 
+// The band arrays (kv_lo, q_hi of ops/attention.py:_band_bounds): both or
+// neither, and only with causal and without kvmask. The kernels clamp what
+// the arrays hold, so only their storage is checked. Returns whether a band
+// was given.
+bool flash_check_band(const c10::optional<at::Tensor>& kv_lo,
+                      const c10::optional<at::Tensor>& q_hi,
+                      const at::Tensor& q, bool causal, bool has_kvmask,
+                      const char* who) {
+  const bool has_lo = kv_lo.has_value() && kv_lo->defined();
+  const bool has_hi = q_hi.has_value() && q_hi->defined();
+  TORCH_CHECK(has_lo == has_hi, who,
+              ": kv_lo and q_hi must be given together");
+  if (!has_lo) return false;
+  TORCH_CHECK(causal && !has_kvmask, who,
+              ": a band (kv_lo, q_hi) requires causal and no kvmask");
+  for (const at::Tensor* t : {&*kv_lo, &*q_hi})
+    TORCH_CHECK(t->is_cuda() && t->device() == q.device() &&
+                    t->scalar_type() == at::kInt && t->is_contiguous() &&
+                    t->numel() == q.size(0) * q.size(1),
+                who, ": kv_lo and q_hi must be contiguous int32 [B,S] "
+                "tensors on q's device");
+  return true;
+}
+
 std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k,
                                        at::Tensor v, bool causal,
                                        double scale,
-                                       c10::optional<at::Tensor> kvmask) {
+                                       c10::optional<at::Tensor> kvmask,
+                                       c10::optional<at::Tensor> kv_lo,
+                                       c10::optional<at::Tensor> q_hi) {
   flash_check_qkv(q, k, v, "flash_attn_fwd");
   int B = q.size(0), S = q.size(1), Hq = q.size(2), D = q.size(3);
   int Hk = k.size(2);
   const float* mp = flash_check_kvmask(kvmask, q);
+  const bool band =
+      flash_check_band(kv_lo, q_hi, q, causal, mp != nullptr, "flash_attn_fwd");
   // scale == 0 selects the default softmax scale 1/sqrt(D)
   const float fscale =
       scale == 0.0 ? 1.0f / std::sqrt((float)D) : (float)scale;
@@ -418,25 +535,19 @@ std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k,
   TORCH_CHECK(nwg * 512 <= UINT32_MAX, "flash_attn_fwd: ", nwg,
               " workgroups of 512 threads exceed the 1-D grid limit");
   dim3 grid((unsigned)nwg);
-  if (D == 128) {
-    hipLaunchKernelGGL(flash_fwd_v6_kernel<128>, grid, dim3(512), 0,
-                       stream.stream(),
-                       reinterpret_cast<const short*>(q.data_ptr()),
-                       reinterpret_cast<const short*>(k.data_ptr()),
-                       reinterpret_cast<const short*>(v.data_ptr()),
-                       reinterpret_cast<short*>(out.data_ptr()),
-                       lse.data_ptr<float>(), mp, B, S, Hq, Hk, fscale,
-                       causal ? 1 : 0);
-  } else {
-    hipLaunchKernelGGL(flash_fwd_v6_kernel<64>, grid, dim3(512), 0,
-                       stream.stream(),
-                       reinterpret_cast<const short*>(q.data_ptr()),
-                       reinterpret_cast<const short*>(k.data_ptr()),
-                       reinterpret_cast<const short*>(v.data_ptr()),
-                       reinterpret_cast<short*>(out.data_ptr()),
-                       lse.data_ptr<float>(), mp, B, S, Hq, Hk, fscale,
-                       causal ? 1 : 0);
-  }
+  if (band)  // the forward is q-outer: it reads kv_lo only
+    flash_fwd_band_launch(D, grid, stream.stream(), q.data_ptr(),
+                          k.data_ptr(), v.data_ptr(), out.data_ptr(),
+                          lse.data_ptr<float>(), B, S, Hq, Hk, fscale,
+                          kv_lo->data_ptr<int>());
+  else
+    flash_fwd_launch<false>(D, grid, stream.stream(), q.data_ptr(),
+                            k.data_ptr(), v.data_ptr(), out.data_ptr(),
+                            lse.data_ptr<float>(), mp, B, S, Hq, Hk, fscale,
+                            causal ? 1 : 0, nullptr);
   HIP_CHECK_KERNEL();
   return {out, lse};
 }
+
+#endif  // DSAMD_FLASH_BAND_TU
+

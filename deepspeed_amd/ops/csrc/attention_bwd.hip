@@ -42,6 +42,32 @@
 //     same rows (pass 1: Q / dO; pass 2: K / V), get ids of one residue mod 8
 //     and so share an XCD and its L2, causal-heaviest first (key block 0; the
 //     last q block); every XCD gets the same work.
+//   - BAND (template parameter of both passes; sliding window and packed
+//     documents): row i sees keys kv_lo[i] .. i. kv_lo is a non-decreasing
+//     int32 [B,S] array and q_hi its inverse: q_hi[j] is one past the last
+//     row that admits key j, also non-decreasing. Each pass reads the array
+//     indexed by what it has on the lane, so each needs one extra value per
+//     lane-resident row / key and no LDS.
+//     pass 2 (q on the lane) holds kv_lo of its rows: predicate `gkv >= lo`.
+//       The block's first row has its smallest bound, so the key steps and
+//       the DMA prologue start at step kv_lo[qbase] / 32. A wave skips a step
+//       that ends at or before kv_lo of its first row, and a step is interior
+//       only if it also starts at or after kv_lo of the wave's last in-range
+//       row (the wave's largest bound).
+//     pass 1 (key on the lane) holds q_hi of its key: predicate `gq < hi`.
+//       The block's last in-range key has its largest bound, so the q steps
+//       of every head of the group end at that q_hi, rounded up to a whole
+//       step and capped at S, instead of at S. A wave skips a step that
+//       starts at or after q_hi of its last key, and a step is interior only
+//       if it also ends at or before q_hi of the wave's first key.
+//     The wave and block bounds are scalar, so EXEC stays full around the
+//     transposed reads. Every value read from the arrays is clamped into
+//     [0, S], the first key step to the last causal one and the q range to at
+//     least one step: a wrong array mis-masks but reads nothing outside q,
+//     k, v, dout and the Sp scratch. With kv_lo = 0 and q_hi = S both passes
+//     visit the steps of the plain kernels in their order and are
+//     bit-identical to them; BAND = false compiles to the code it was before
+//     the parameter existed (pass 1 at D 128: still 161 registers).
 // Results are written transposed from the accumulators: 4 consecutive d per
 // lane, one 8-byte store.
 //
@@ -224,7 +250,9 @@ DEV_INLINE void unrotate_row(f32x4_t* acc /* [NDT] tiles, STRIDE apart */,
 // ---------------------------------------------------------------------------
 // ROPE: q and k are the rotated tensors forward attended over; dk is returned
 // with respect to the un-rotated k (rope_cos/rope_sin: fp32 [>=S, DH/2]).
-template <int DH, int KTW, int NW, bool ROPE>
+// BAND: causal is taken as given, kvmask as absent, and q_hi ([B,S] int32,
+// non-decreasing along S) is one past the last q row that admits each key.
+template <int DH, int KTW, int NW, bool ROPE, bool BAND>
 __launch_bounds__(64 * NW, DH == 128 ? 3 : 4)
 __global__ void flash_bwd_dkv_kernel(
     const short* __restrict__ q,     // [B,S,Hq,D]
@@ -238,7 +266,12 @@ __global__ void flash_bwd_dkv_kernel(
     short* __restrict__ dv,          // [B,S,Hk,D]
     const float* __restrict__ rope_cos,  // ROPE only, else null
     const float* __restrict__ rope_sin,
-    int B, int S, int Sp, int Hq, int Hk, float scale, int causal) {
+    int B, int S, int Sp, int Hq, int Hk, float scale, int causal,
+    const int* __restrict__ q_hi) {  // BAND only, else null
+  if constexpr (BAND) {
+    causal = 1;
+    kvmask = nullptr;
+  }
   constexpr int NKS = DH / 32;        // k-slices of the S / dP products
   constexpr int NDT = DH / 16;        // d-tiles of dK^T / dV^T
   constexpr int IMG = TS * DH * 2;    // bytes per image
@@ -276,6 +309,7 @@ __global__ void flash_bwd_dkv_kernel(
   // K/V fragments in registers (B operands: key on the lane)
   bf16x8_t kfrag[KTW][NKS], vfrag[KTW][NKS];
   float maskv[KTW];
+  int hi_l[KTW] = {};  // BAND: q_hi of the lane's key
 #pragma unroll
   for (int kt = 0; kt < KTW; ++kt) {
     const int krow = wk + 16 * kt + l15;
@@ -290,6 +324,26 @@ __global__ void flash_bwd_dkv_kernel(
           *reinterpret_cast<const bf16x8_t*>(vs + ks_i * 32 + l4 * 8);
     }
     maskv[kt] = (kvmask && krow < S) ? kvmask[(long long)b * S + krow] : 0.f;
+    if constexpr (BAND)
+      hi_l[kt] = band_clamp(q_hi[(long long)b * S + srow], S);
+  }
+  // BAND: the wave's and the block's q ranges, scalar (uniform addresses), so
+  // the branches on them are scalar and EXEC stays full. q_hi does not
+  // decrease, so a range's first key has its smallest bound, its last
+  // in-range key the largest.
+  int whi_first = 0, whi_last = 0, q_end = S;
+  if constexpr (BAND) {
+    const int* hip_ = q_hi + (long long)b * S;
+    whi_first = __builtin_amdgcn_readfirstlane(
+        band_clamp(hip_[min(wk, S - 1)], S));
+    whi_last = __builtin_amdgcn_readfirstlane(
+        band_clamp(hip_[min(wk + WRK - 1, S - 1)], S));
+    // no row from q_hi of the block's last in-range key on admits any key of
+    // the block: the q steps end there (rounded up to whole steps, within S,
+    // and at least one step, whatever the array holds)
+    const int bhi = __builtin_amdgcn_readfirstlane(
+        band_clamp(hip_[min(kv_base + BRK - 1, S - 1)], S));
+    q_end = min(S, max((bhi + TS - 1) / TS * TS, kv_base + TS));
   }
   // Consume them here, before the first DMA is issued: the compiler then
   // waits for these loads now, not with a vmcnt(0) at their first use inside
@@ -302,6 +356,7 @@ __global__ void flash_bwd_dkv_kernel(
       asm volatile("" : "+v"(vfrag[kt][ks_i]));
     }
     asm volatile("" : "+v"(maskv[kt]));
+    if constexpr (BAND) asm volatile("" : "+v"(hi_l[kt]));
   }
 
   f32x4_t dk_acc[NDT][KTW], dv_acc[NDT][KTW];
@@ -314,7 +369,9 @@ __global__ void flash_bwd_dkv_kernel(
     }
 
   const int q_start = causal ? kv_base : 0;  // multiple of 32
-  const int nq = (S - q_start + TS - 1) / TS;
+  // q_end is S, or under BAND the end of the block's band: every head of
+  // the group walks q_start .. q_end
+  const int nq = (q_end - q_start + TS - 1) / TS;
   const int total = G * nq;
 
   static_assert(NW >= SPI || SPI % NW == 0,
@@ -355,7 +412,7 @@ __global__ void flash_bwd_dkv_kernel(
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     qb_nx += TS;
-    if (qb_nx >= S) {
+    if (qb_nx >= q_end) {
       qb_nx = q_start;
       ++g_nx;
     }
@@ -363,8 +420,11 @@ __global__ void flash_bwd_dkv_kernel(
 
     // wave-uniform: nothing admissible in this 32 x 32 strip
     if (wk >= S || (causal && qb + TS - 1 < wk)) continue;
+    // BAND: nor past the band of the wave's last key
+    if (BAND && qb >= whi_last) continue;
     const bool interior = !kvmask && qb + TS <= S && wk + WRK <= S &&
-                          (!causal || qb >= wk + WRK - 1);
+                          (!causal || qb >= wk + WRK - 1) &&
+                          (!BAND || qb + TS <= whi_first);
     const char* buf = smem + (it & 1) * BUF;
     const float* ld = reinterpret_cast<const float*>(buf + LD_OFF);
 
@@ -418,7 +478,8 @@ __global__ void flash_bwd_dkv_kernel(
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int gq = qb + 16 * qt + 4 * l4 + r;
-            const bool valid = gq < S && gkv < S && (!causal || gq >= gkv);
+            const bool valid = gq < S && gkv < S && (!causal || gq >= gkv) &&
+                               (!BAND || gq < hi_l[kt]);
             float sval = s_acc[qt][kt][r] * scale + maskv[kt];
             float p = valid ? __expf(sval - lrow[qt][r]) : 0.f;
             s_acc[qt][kt][r] = p;
@@ -487,7 +548,9 @@ __global__ void flash_bwd_dkv_kernel(
 // Accumulates dQ^T (d on the register row, q on the lane).
 // ---------------------------------------------------------------------------
 // ROPE: as in pass 1; dq is returned with respect to the un-rotated q.
-template <int DH, bool ROPE>
+// BAND: as in pass 1, with kv_lo ([B,S] int32, non-decreasing along S), the
+// first admissible key of each q row.
+template <int DH, bool ROPE, bool BAND>
 __launch_bounds__(256, 2)
 __global__ void flash_bwd_dq_kernel(
     const short* __restrict__ q, const short* __restrict__ k,
@@ -498,7 +561,12 @@ __global__ void flash_bwd_dq_kernel(
     short* __restrict__ dq,  // [B,S,Hq,D]
     const float* __restrict__ rope_cos,  // ROPE only, else null
     const float* __restrict__ rope_sin,
-    int B, int S, int Sp, int Hq, int Hk, float scale, int causal) {
+    int B, int S, int Sp, int Hq, int Hk, float scale, int causal,
+    const int* __restrict__ kv_lo) {  // BAND only, else null
+  if constexpr (BAND) {
+    causal = 1;
+    kvmask = nullptr;
+  }
   constexpr int NKS = DH / 32;
   constexpr int NDT = DH / 16;
   constexpr int IMG = TS * DH * 2;
@@ -536,10 +604,13 @@ __global__ void flash_bwd_dq_kernel(
   // the lane's row constants (wq + 31 < Sp: the padded copies are in bounds)
   bf16x8_t qfrag[2][NKS], dofrag[2][NKS];
   float lse_l[2], dr_l[2];
+  int lo_l[2] = {};  // BAND: kv_lo of the lane's two rows
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int qrow = wq + 16 * qt + l15;
     const int srow = qrow < S ? qrow : S - 1;
+    if constexpr (BAND)
+      lo_l[qt] = band_clamp(kv_lo[(long long)b * S + srow], S);
     const short* qs = qp + (long long)srow * qrs;
     const short* ds = dop + (long long)srow * qrs;
 #pragma unroll
@@ -572,8 +643,26 @@ __global__ void flash_bwd_dq_kernel(
     }
   };
 
-  issue(0, 0);
-  for (int t = 0; t < n_tiles; ++t) {
+  // BAND: kv_lo does not decrease, so no row of the block admits a key below
+  // kv_lo[qbase] (qbase < S: the grid has ceil(S / BR) blocks): the steps and
+  // the prologue start at that key's step, at most the last one whatever the
+  // array holds. A wave's own bounds are kv_lo of its first row (steps that
+  // end at or before it hold nothing for the wave) and of its last in-range
+  // row (steps from it on need no lower predicate). All three are scalar.
+  int t0 = 0, wlo_first = 0, wlo_last = 0;
+  if constexpr (BAND) {
+    const int* lop = kv_lo + (long long)b * S;
+    const int wq_s = __builtin_amdgcn_readfirstlane(wq);
+    t0 = min(__builtin_amdgcn_readfirstlane(band_clamp(lop[qbase], S)) / TS,
+             n_tiles - 1);
+    wlo_first = __builtin_amdgcn_readfirstlane(
+        band_clamp(lop[min(wq_s, S - 1)], S));
+    wlo_last = __builtin_amdgcn_readfirstlane(
+        band_clamp(lop[min(wq_s + WR - 1, S - 1)], S));
+  }
+
+  issue(t0 * TS, t0 & 1);
+  for (int t = t0; t < n_tiles; ++t) {
     const int kvb = t * TS;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -581,8 +670,10 @@ __global__ void flash_bwd_dq_kernel(
 
     // wave-uniform: nothing admissible in this 32 x 32 strip
     if (wq >= S || (causal && kvb > wq + WR - 1)) continue;
+    if (BAND && kvb + TS <= wlo_first) continue;
     const bool interior = !mp && kvb + TS <= S && wq + WR <= S &&
-                          (!causal || kvb + TS - 1 <= wq);
+                          (!causal || kvb + TS - 1 <= wq) &&
+                          (!BAND || kvb >= wlo_last);
     const char* buf = smem + (t & 1) * BUF;
 
     // ---- S^T = K Q^T ; dP^T - Drow (2 key-tiles x 2 q-tiles) -------------
@@ -633,7 +724,8 @@ __global__ void flash_bwd_dq_kernel(
 #pragma unroll
           for (int qt = 0; qt < 2; ++qt) {
             const int gq = wq + 16 * qt + l15;
-            const bool valid = gq < S && gkv < S && (!causal || gkv <= gq);
+            const bool valid = gq < S && gkv < S && (!causal || gkv <= gq) &&
+                               (!BAND || gkv >= lo_l[qt]);
             float sval = s_acc[kt][qt][r] * scale + mv;
             float p = valid ? __expf(sval - lse_l[qt]) : 0.f;
             dp_acc[kt][qt][r] = p * dp_acc[kt][qt][r] * scale;
@@ -685,57 +777,104 @@ __global__ void flash_bwd_dq_kernel(
 
 }  // namespace bwd
 
-template <int DH, bool ROPE>
+static const short* sp(const at::Tensor& t) {
+  return reinterpret_cast<const short*>(t.data_ptr());
+}
+static short* spm(at::Tensor& t) {
+  return reinterpret_cast<short*>(t.data_ptr());
+}
+
+// Pass 1 and pass 2 over the row constants drow, lseP ([B,Hq,Sp]) that the
+// pre-pass wrote.
+template <int DH, bool ROPE, bool BAND>
 static void launch_bwd(at::Tensor& q, at::Tensor& k, at::Tensor& v,
-                       at::Tensor& dout, at::Tensor& out, at::Tensor& lse,
+                       at::Tensor& dout, at::Tensor& drow, at::Tensor& lseP,
                        at::Tensor& dq, at::Tensor& dk, at::Tensor& dv,
                        const float* mp, const float* cosp, const float* sinp,
                        int B, int S, int Hq, int Hk, float scale,
-                       int causal) {
+                       int causal, const int* lop, const int* hip_) {
   auto stream = c10::hip::getCurrentHIPStream();
-  // row constants, fully rewritten (pad included) by the pre-pass of every
-  // call: the only scratch left
-  const int Sp = (S + bwd::BR - 1) / bwd::BR * bwd::BR;
-  auto drow = at::empty({B, Hq, Sp}, q.options().dtype(at::kFloat));
-  auto lseP = at::empty({B, Hq, Sp}, q.options().dtype(at::kFloat));
-  auto sp = [](const at::Tensor& t) {
-    return reinterpret_cast<const short*>(t.data_ptr());
-  };
-  auto spm = [](at::Tensor& t) {
-    return reinterpret_cast<short*>(t.data_ptr());
-  };
-  dim3 grid0(Sp / bwd::PT, B * Hq);
-  hipLaunchKernelGGL(bwd::bwd_preprocess<DH>, grid0, dim3(256), 0,
-                     stream.stream(), sp(dout), sp(out),
-                     lse.data_ptr<float>(), drow.data_ptr<float>(),
-                     lseP.data_ptr<float>(), B, S, Sp, Hq);
-  HIP_CHECK_KERNEL();
+  const int Sp = drow.size(2);
   // 1-D: the kernel maps the workgroup id to (key block, b * Hk + kv head)
   // with bwd_wgmap::wg_index, so the grid is exactly their product
   const int nkb1 = (S + bwd::BRK1 - 1) / bwd::BRK1;
   dim3 grid1(nkb1 * B * Hk);
   hipLaunchKernelGGL(
-      (bwd::flash_bwd_dkv_kernel<DH, bwd::KTW1, bwd::NW1, ROPE>), grid1,
+      (bwd::flash_bwd_dkv_kernel<DH, bwd::KTW1, bwd::NW1, ROPE, BAND>), grid1,
       dim3(64 * bwd::NW1), 0, stream.stream(), sp(q), sp(k), sp(v), sp(dout),
       lseP.data_ptr<float>(), drow.data_ptr<float>(), mp, spm(dk), spm(dv),
-      cosp, sinp, B, S, Sp, Hq, Hk, scale, causal);
+      cosp, sinp, B, S, Sp, Hq, Hk, scale, causal, hip_);
   HIP_CHECK_KERNEL();
   // 1-D as well: (q block, b * Hq + q head) by bwd_wgmap::q_index
   const long long nwg2 = (long long)(Sp / bwd::BR) * B * Hq;
   TORCH_CHECK(nwg2 * 256 <= UINT32_MAX, "flash_attn_bwd: ", nwg2,
               " workgroups of 256 threads exceed the 1-D grid limit");
   dim3 grid2((unsigned)nwg2);
-  hipLaunchKernelGGL((bwd::flash_bwd_dq_kernel<DH, ROPE>), grid2, dim3(256), 0,
-                     stream.stream(), sp(q), sp(k), sp(v), sp(dout),
-                     lseP.data_ptr<float>(), drow.data_ptr<float>(), mp,
-                     spm(dq), cosp, sinp, B, S, Sp, Hq, Hk, scale, causal);
+  hipLaunchKernelGGL((bwd::flash_bwd_dq_kernel<DH, ROPE, BAND>), grid2,
+                     dim3(256), 0, stream.stream(), sp(q), sp(k), sp(v),
+                     sp(dout), lseP.data_ptr<float>(), drow.data_ptr<float>(),
+                     mp, spm(dq), cosp, sinp, B, S, Sp, Hq, Hk, scale, causal,
+                     lop);
   HIP_CHECK_KERNEL();
 }
+
+// Both passes, head dimension and ROPE chosen at run time.
+template <bool BAND>
+static void flash_bwd_launch(at::Tensor& q, at::Tensor& k, at::Tensor& v,
+                             at::Tensor& dout, at::Tensor& drow,
+                             at::Tensor& lseP, at::Tensor& dq, at::Tensor& dk,
+                             at::Tensor& dv, const float* mp,
+                             const float* cosp, const float* sinp,
+                             float scale, int causal, const int* lop,
+                             const int* hip_) {
+  const int B = q.size(0), S = q.size(1), Hq = q.size(2), D = q.size(3);
+  const int Hk = k.size(2);
+#define DSAMD_LAUNCH_BWD(DH_, ROPE_)                                       \
+  launch_bwd<DH_, ROPE_, BAND>(q, k, v, dout, drow, lseP, dq, dk, dv, mp,  \
+                               cosp, sinp, B, S, Hq, Hk, scale, causal,    \
+                               lop, hip_)
+  if (D == 128) {
+    if (cosp) DSAMD_LAUNCH_BWD(128, true); else DSAMD_LAUNCH_BWD(128, false);
+  } else {
+    if (cosp) DSAMD_LAUNCH_BWD(64, true); else DSAMD_LAUNCH_BWD(64, false);
+  }
+#undef DSAMD_LAUNCH_BWD
+}
+
+// The BAND instantiations live in a translation unit of their own,
+// attention_bwd_band.hip, which includes this file with DSAMD_FLASH_BAND_TU
+// set and is built without packed fp32 instructions (ops/build.py,
+// NO_PACKED_FP32, has the reason); this unit keeps the pre-pass, the plain
+// instantiations and the build they were validated with.
+void flash_bwd_band_launch(at::Tensor& q, at::Tensor& k, at::Tensor& v,
+                           at::Tensor& dout, at::Tensor& drow,
+                           at::Tensor& lseP, at::Tensor& dq, at::Tensor& dk,
+                           at::Tensor& dv, const float* cosp,
+                           const float* sinp, float scale, const int* kv_lo,
+                           const int* q_hi);
+
+#ifdef DSAMD_FLASH_BAND_TU
+
+void flash_bwd_band_launch(at::Tensor& q, at::Tensor& k, at::Tensor& v,
+                           at::Tensor& dout, at::Tensor& drow,
+                           at::Tensor& lseP, at::Tensor& dq, at::Tensor& dk,
+                           at::Tensor& dv, const float* cosp,
+                           const float* sinp, float scale, const int* kv_lo,
+                           const int* q_hi) {
+  flash_bwd_launch<true>(q, k, v, dout, drow, lseP, dq, dk, dv, nullptr, cosp,
+                         sinp, scale, 1, kv_lo, q_hi);
+}
+
+#else
 
 void flash_check_qkv(const at::Tensor& q, const at::Tensor& k,
                      const at::Tensor& v, const char* who);
 const float* flash_check_kvmask(const c10::optional<at::Tensor>& kvmask,
                                 const at::Tensor& q);
+bool flash_check_band(const c10::optional<at::Tensor>& kv_lo,
+                      const c10::optional<at::Tensor>& q_hi,
+                      const at::Tensor& q, bool causal, bool has_kvmask,
+                      const char* who);
 void check_rope_table(const at::Tensor& cos, const at::Tensor& sin,
                       const at::Tensor& ref, long long S, int D,
                       const char* who);
@@ -746,7 +885,9 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
                                        bool causal, double scale,
                                        c10::optional<at::Tensor> kvmask,
                                        c10::optional<at::Tensor> cos,
-                                       c10::optional<at::Tensor> sin) {
+                                       c10::optional<at::Tensor> sin,
+                                       c10::optional<at::Tensor> kv_lo,
+                                       c10::optional<at::Tensor> q_hi) {
   flash_check_qkv(q, k, v, "flash_attn_bwd");
   CHECK_ARG(dout, at::kBFloat16);
   CHECK_ARG(out, at::kBFloat16);
@@ -757,11 +898,12 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
   TORCH_CHECK(dout.sizes() == q.sizes() && out.sizes() == q.sizes(),
               "flash_attn_bwd: dout and out must have q's shape");
   int B = q.size(0), S = q.size(1), Hq = q.size(2), D = q.size(3);
-  int Hk = k.size(2);
   TORCH_CHECK(lse.dim() == 3 && lse.size(0) == B && lse.size(1) == Hq &&
                   lse.size(2) == S,
               "flash_attn_bwd: lse must be [B,Hq,S]");
   const float* mp = flash_check_kvmask(kvmask, q);
+  const bool band =
+      flash_check_band(kv_lo, q_hi, q, causal, mp != nullptr, "flash_attn_bwd");
   // scale == 0 selects the default softmax scale 1/sqrt(D), as in forward
   const float fscale =
       scale == 0.0 ? 1.0f / std::sqrt((float)D) : (float)scale;
@@ -780,15 +922,25 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
     cosp = cos->data_ptr<float>();
     sinp = sin->data_ptr<float>();
   }
-  const int ic = causal ? 1 : 0;
-#define DSAMD_LAUNCH_BWD(DH_, ROPE_)                                        \
-  launch_bwd<DH_, ROPE_>(q, k, v, dout, out, lse, dq, dk, dv, mp, cosp, sinp, \
-                         B, S, Hq, Hk, fscale, ic)
-  if (D == 128) {
-    if (rope) DSAMD_LAUNCH_BWD(128, true); else DSAMD_LAUNCH_BWD(128, false);
-  } else {
-    if (rope) DSAMD_LAUNCH_BWD(64, true); else DSAMD_LAUNCH_BWD(64, false);
-  }
-#undef DSAMD_LAUNCH_BWD
+  // row constants, fully rewritten (pad included) by the pre-pass of every
+  // call: the only scratch left
+  const int Sp = (S + bwd::BR - 1) / bwd::BR * bwd::BR;
+  auto drow = at::empty({B, Hq, Sp}, q.options().dtype(at::kFloat));
+  auto lseP = at::empty({B, Hq, Sp}, q.options().dtype(at::kFloat));
+  auto pre = D == 128 ? bwd::bwd_preprocess<128> : bwd::bwd_preprocess<64>;
+  hipLaunchKernelGGL(pre, dim3(Sp / bwd::PT, B * Hq), dim3(256), 0,
+                     c10::hip::getCurrentHIPStream().stream(), sp(dout),
+                     sp(out), lse.data_ptr<float>(), drow.data_ptr<float>(),
+                     lseP.data_ptr<float>(), B, S, Sp, Hq);
+  HIP_CHECK_KERNEL();
+  if (band)  // pass 1 (key-outer) reads q_hi, pass 2 (q-outer) kv_lo
+    flash_bwd_band_launch(q, k, v, dout, drow, lseP, dq, dk, dv, cosp, sinp,
+                          fscale, kv_lo->data_ptr<int>(),
+                          q_hi->data_ptr<int>());
+  else
+    flash_bwd_launch<false>(q, k, v, dout, drow, lseP, dq, dk, dv, mp, cosp,
+                            sinp, fscale, causal ? 1 : 0, nullptr, nullptr);
   return {dq, dk, dv};
 }
+
+#endif  // DSAMD_FLASH_BAND_TU

@@ -41,14 +41,18 @@ std::vector<at::Tensor> fp8_cast_transpose(at::Tensor x, at::Tensor scale,
 std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k,
                                        at::Tensor v, bool causal,
                                        double scale,
-                                       c10::optional<at::Tensor> kvmask);
+                                       c10::optional<at::Tensor> kvmask,
+                                       c10::optional<at::Tensor> kv_lo,
+                                       c10::optional<at::Tensor> q_hi);
 std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
                                        at::Tensor v, at::Tensor dout,
                                        at::Tensor out, at::Tensor lse,
                                        bool causal, double scale,
                                        c10::optional<at::Tensor> kvmask,
                                        c10::optional<at::Tensor> cos,
-                                       c10::optional<at::Tensor> sin);
+                                       c10::optional<at::Tensor> sin,
+                                       c10::optional<at::Tensor> kv_lo,
+                                       c10::optional<at::Tensor> q_hi);
 void multi_tensor_adagrad(std::vector<at::Tensor> params,
                           std::vector<at::Tensor> grads,
                           std::vector<at::Tensor> sq_accums, double lr,
@@ -177,12 +181,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // any other value is used as given.
   m.def("flash_attn_fwd", &flash_attn_fwd, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("causal") = true, py::arg("scale") = 0.0,
-        py::arg("kvmask") = c10::nullopt);
+        py::arg("kvmask") = c10::nullopt, py::arg("kv_lo") = c10::nullopt,
+        py::arg("q_hi") = c10::nullopt);
   m.def("flash_attn_bwd", &flash_attn_bwd, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("dout"), py::arg("out"), py::arg("lse"),
         py::arg("causal") = true, py::arg("scale") = 0.0,
         py::arg("kvmask") = c10::nullopt, py::arg("cos") = c10::nullopt,
-        py::arg("sin") = c10::nullopt);
+        py::arg("sin") = c10::nullopt, py::arg("kv_lo") = c10::nullopt,
+        py::arg("q_hi") = c10::nullopt);
   m.def("multi_tensor_adagrad", &multi_tensor_adagrad, py::arg("params"),
         py::arg("grads"), py::arg("sq_accums"), py::arg("lr"),
         py::arg("eps") = 1e-8, py::arg("weight_decay") = 0.0,

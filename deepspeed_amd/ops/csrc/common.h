@@ -49,6 +49,10 @@ struct alignas(16) f32x4 {
   float v[4];
 };
 
+// An entry of a flash attention band array (kv_lo, q_hi), whatever it holds,
+// as a row / key count in [0, S].
+DEV_INLINE int band_clamp(int x, int S) { return min(max(x, 0), S); }
+
 DEV_INLINE float bf2f(short b) {
   union {
     float f;
