@@ -12,8 +12,9 @@ slots — paged/blocked KV is not needed to avoid fragmentation at this
 scale, so slot granularity keeps the layout hipGraph-friendly). Ragged
 lengths are handled with per-row RoPE positions (`positions` arg). On the
 GPU (bf16, head_dim 64/128) decode attention runs the `ragged_decode` HIP
-kernel straight over the pool; elsewhere an additive length mask goes
-through SDPA.
+kernel straight over the pool, or `ragged_decode_gqa` (MFMA split-KV) for the
+GQA groups and sliding windows `ragged_decode` does not serve and whenever
+`mfma_decode=True`; elsewhere an additive length mask goes through SDPA.
 
 `fused_step=True` (opt-in) is Dynamic SplitFuse proper: every step packs
 its prefill chunks and one token per decoding request into ONE ragged
@@ -62,7 +63,22 @@ class RaggedKVCache:
     """One layer's slot-granular KV pool with per-slot lengths."""
 
     def __init__(self, max_batch, max_seq, n_kv, d, dtype, device,
-                 rope=None, fp8=False):
+                 rope=None, fp8=False, window=None, mfma_decode=False):
+        # window: a token attends the last `window` positions, itself
+        # included (LlamaConfig.sliding_window). The pool still keeps every
+        # position; decode and the masked fallbacks read the band only.
+        # mfma_decode: every decode step runs `ragged_decode_gqa`, also at
+        # the shapes `ragged_decode` serves. max_len: the engine's host-side
+        # bound on this step's lengths (spares that kernel its host read).
+        if window is not None and window < 1:
+            raise ValueError(f"window must be >= 1, got {window}")
+        if window is not None and fp8:
+            raise NotImplementedError(
+                f"sliding_window={window} with the fp8 KV slot pool: the fp8 "
+                "ragged kernels have no window")
+        self.window = window
+        self.mfma_decode = mfma_decode
+        self.max_len = None
         # fp8: e4m3fn codes plus one fp32 scale per (slot, position, kv head)
         # row -- ops.functional.kv_quantize. Needs `rope` (every ragged step
         # appends through rope_append) and head_dim 64 / 128.
@@ -151,12 +167,20 @@ class RaggedKVCache:
             self.attn_mask = None
             self.ragged = (self.k, self.v, rows, lens)
             return q, k, v
-        maxlen = int(lens.max())
-        ar = torch.arange(maxlen, device=k.device)
-        valid = ar.unsqueeze(0) < lens.unsqueeze(1)          # [n, maxlen]
-        self.attn_mask = torch.where(
-            valid, 0.0, float("-inf")).view(-1, 1, 1, maxlen).float()
+        self.attn_mask = self._decode_mask(lens)
+        maxlen = self.attn_mask.shape[-1]
         return q, self.k[rows, :maxlen], self.v[rows, :maxlen]
+
+    def _decode_mask(self, lens):
+        """Additive [n,1,1,maxlen] mask of the masked decode fallback: row i
+        sees positions [lens[i] - window, lens[i])."""
+        maxlen = int(lens.max())
+        ar = torch.arange(maxlen, device=lens.device)
+        valid = ar.unsqueeze(0) < lens.unsqueeze(1)          # [n, maxlen]
+        if self.window is not None:
+            valid &= ar.unsqueeze(0) >= lens.unsqueeze(1) - self.window
+        return torch.where(
+            valid, 0.0, float("-inf")).view(-1, 1, 1, maxlen).float()
 
     def update(self, k, v):
         if self.fused is not None:           # [1, T, Hk, D] packed tokens
@@ -190,8 +214,10 @@ class RaggedKVCache:
             total = o + S
             q_pos = torch.arange(o, total, device=k.device).view(S, 1)
             k_pos = torch.arange(total, device=k.device).view(1, total)
-            self.attn_mask = torch.where(k_pos <= q_pos, 0.0,
-                                         float("-inf")) \
+            vis = k_pos <= q_pos
+            if self.window is not None:
+                vis &= k_pos > q_pos - self.window
+            self.attn_mask = torch.where(vis, 0.0, float("-inf")) \
                 .view(1, 1, S, total).to(torch.float32)
             if self.fp8:
                 return (kv_dequantize(self.k[s:s + 1, :total],
@@ -210,11 +236,8 @@ class RaggedKVCache:
             self.ragged = (self.k, self.v, rows.contiguous(),
                            lens.contiguous())
             return k, v  # attention reads from the pool via the kernel
-        maxlen = int(lens.max())
-        ar = torch.arange(maxlen, device=k.device)
-        valid = ar.unsqueeze(0) < lens.unsqueeze(1)          # [n, maxlen]
-        self.attn_mask = torch.where(
-            valid, 0.0, float("-inf")).view(-1, 1, 1, maxlen).float()
+        self.attn_mask = self._decode_mask(lens)
+        maxlen = self.attn_mask.shape[-1]
         return self.k[rows, :maxlen], self.v[rows, :maxlen]
 
 
@@ -223,7 +246,7 @@ class ContinuousBatchingEngine:
 
     def __init__(self, model, max_batch=8, max_seq=None, device=None,
                  prefill_chunk=None, prefill_budget=None, fused_step=False,
-                 fused_kv_append=False, kv_dtype=None):
+                 fused_kv_append=False, kv_dtype=None, mfma_decode=False):
         self.model = model
         cfg = model.cfg if hasattr(model, "cfg") else model.config
         self.cfg = cfg
@@ -258,10 +281,33 @@ class ContinuousBatchingEngine:
         self.kv_fp8 = kv_dtype is not None
         if self.kv_fp8 and not fused_kv_append:
             raise ValueError("kv_dtype='fp8' needs fused_kv_append=True")
+        # sliding_window models: the decode step and the masked fallbacks
+        # attend the band; the steps without a window kernel are refused here
+        window = getattr(cfg, "sliding_window", None)
+        if window is not None and fused_step:
+            raise NotImplementedError(
+                f"sliding_window={window} with fused_step=True: "
+                "ragged_prefill has no window")
+        if window is not None and self.kv_fp8:
+            raise NotImplementedError(
+                f"sliding_window={window} with kv_dtype='fp8': the fp8 "
+                "ragged kernels have no window")
+        group = cfg.num_attention_heads // cfg.num_key_value_heads
+        on_kernel = (torch.device(self.device).type == "cuda"
+                     and dtype == torch.bfloat16
+                     and cfg.head_dim in (64, 128))
+        if fused_step and on_kernel and group not in (1, 2, 4, 8):
+            raise NotImplementedError(
+                f"fused_step=True with GQA group {group}: ragged_prefill "
+                "serves groups 1, 2, 4 and 8")
+        # mfma_decode (opt-in): every decode step runs `ragged_decode_gqa`,
+        # sized from the host-side request lengths (no device-to-host read)
+        self.mfma_decode = mfma_decode
         self.caches = [RaggedKVCache(max_batch, self.max_seq,
                                      cfg.num_key_value_heads, cfg.head_dim,
                                      dtype, self.device, rope=rope,
-                                     fp8=self.kv_fp8)
+                                     fp8=self.kv_fp8, window=window,
+                                     mfma_decode=mfma_decode)
                        for _ in range(cfg.num_hidden_layers)]
         # Dynamic SplitFuse-style scheduling (ref FastGen): bound the
         # prompt tokens processed per step so long prompts stream in
@@ -344,16 +390,22 @@ class ContinuousBatchingEngine:
         positions = self.caches[0].lens[rows].view(-1, 1)
         pos = positions.view(-1)
         new_lens = pos + 1 if self.fused_kv_append else None
+        # every running request holds prompt + generated - 1 cached tokens;
+        # this step appends one
+        max_len = min(self.max_seq, max(len(r.prompt) + len(r.generated)
+                                        for r in active))
         for c in self.caches:
             c.rows = rows
             c.pos = pos
             c.new_lens = new_lens
+            c.max_len = max_len
         logits = self.model(last, kv_caches=self.caches,
                             positions=positions)
         for c in self.caches:
             c.rows = None
             c.pos = None
             c.new_lens = None
+            c.max_len = None
         for r, row in zip(active, logits[:, -1]):
             r.generated.append(self._sample(row, r))
             self._check_done(r)

@@ -104,14 +104,21 @@ class LlamaAttention(nn.Module):
         # and the plain prefill; the paths that cannot honour it refuse
         win = getattr(self.cfg, "sliding_window", None)
         wkw = {} if win is None else {"window": win}
-        if win is not None and (getattr(kv_cache, "fuses_rope", False)
-                                or getattr(kv_cache, "ragged", None)
-                                is not None
-                                or getattr(kv_cache, "fused", None)
-                                is not None):
-            raise NotImplementedError(
-                "sliding_window is not supported by the ragged / fp8 slot-pool "
-                "attention kernels: they would attend the whole context")
+        if win is not None and kv_cache is not None:
+            # the slot-pool steps that would attend the whole context
+            if getattr(kv_cache, "fused", None) is not None:
+                raise NotImplementedError(
+                    f"sliding_window={win} with the fused serving step: "
+                    "ragged_prefill has no window")
+            if getattr(kv_cache, "fp8", False):
+                raise NotImplementedError(
+                    f"sliding_window={win} with the fp8 KV slot pool: the "
+                    "fp8 ragged kernels have no window")
+            if hasattr(kv_cache, "ragged") and \
+                    getattr(kv_cache, "window", None) != win:
+                raise NotImplementedError(
+                    f"sliding_window={win}: the ragged cache was not built "
+                    "with this window")
         # RoPE uses the caller's cos/sin slice (seq-offset aware under SP)
         if getattr(kv_cache, "fuses_rope", False):
             # ragged serving step with fused_kv_append: RoPE of q and k, the
@@ -149,14 +156,21 @@ class LlamaAttention(nn.Module):
                 o = ragged_prefill_attention(q[0], kv_cache.k, kv_cache.v,
                                              fb)
             elif rg is not None:
-                # ragged decode straight from the slot pool (no copies)
-                from ..ops.loader import get_ext
-                o = get_ext(required=True).ragged_decode(
-                    q.contiguous(), *rg)
+                # ragged decode straight from the slot pool (no copies),
+                # over the cache's window
+                from ..ops.functional import ragged_decode_attention
+                o = ragged_decode_attention(
+                    q, *rg, window=getattr(kv_cache, "window", None),
+                    max_len=getattr(kv_cache, "max_len", None),
+                    mfma=getattr(kv_cache, "mfma_decode", False))
             else:
                 mask = getattr(kv_cache, "attn_mask", None)
                 causal = S > 1  # prefill is causal; decode sees all past
-                if win is not None and k.shape[1] > win:
+                # a mask built by a cache that declares this window already
+                # carries the band
+                banded = mask is not None and \
+                    getattr(kv_cache, "window", None) == win
+                if win is not None and k.shape[1] > win and not banded:
                     # only a whole-sequence prefill is a band the kernels know
                     if not (causal and mask is None and k.shape[1] == S):
                         raise NotImplementedError(

@@ -48,6 +48,7 @@ def _sources():
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 BAND_UNITS = {"attention_band.hip": "attention.hip",
               "attention_bwd_band.hip": "attention_bwd.hip"}
+NO_PACKED_UNITS = set(BAND_UNITS) | {"ragged_decode_gqa.hip"}
 
 
 def _headers_mtime():
@@ -94,7 +95,8 @@ def build(verbose=True, force=False):
 
     def compile_one(pair):
         src, obj = pair
-        extra = NO_PACKED_FP32 if os.path.basename(src) in BAND_UNITS else []
+        extra = (NO_PACKED_FP32 if os.path.basename(src) in NO_PACKED_UNITS
+                 else [])
         cmd = ["hipcc"] + flags + extra + ["-c", src, "-o", obj]
         if verbose:
             print(f"[ops.build] compiling {os.path.basename(src)}")

@@ -15,6 +15,9 @@ at::Tensor l2norm_sq(std::vector<at::Tensor> tensors);
 at::Tensor fp8_amax(at::Tensor x);
 at::Tensor ragged_decode(at::Tensor q, at::Tensor kpool, at::Tensor vpool,
                          at::Tensor rows, at::Tensor lens, long chunk);
+at::Tensor ragged_decode_gqa(at::Tensor q, at::Tensor kpool, at::Tensor vpool,
+                             at::Tensor rows, at::Tensor lens, long window,
+                             long max_len, long splits);
 at::Tensor ragged_prefill(at::Tensor q, at::Tensor kpool, at::Tensor vpool,
                           at::Tensor desc, long max_qlen, long max_kvlen);
 at::Tensor ragged_rope_append(at::Tensor q, at::Tensor k, at::Tensor v,
@@ -137,6 +140,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ragged_decode", &ragged_decode, py::arg("q"), py::arg("kpool"),
         py::arg("vpool"), py::arg("rows"), py::arg("lens"),
         py::arg("chunk") = 512);
+  m.def("ragged_decode_gqa", &ragged_decode_gqa, py::arg("q"),
+        py::arg("kpool"), py::arg("vpool"), py::arg("rows"), py::arg("lens"),
+        py::arg("window") = 0, py::arg("max_len") = 0, py::arg("splits") = 0);
   m.def("ragged_prefill", &ragged_prefill, py::arg("q"), py::arg("kpool"),
         py::arg("vpool"), py::arg("desc"), py::arg("max_qlen"),
         py::arg("max_kvlen"));

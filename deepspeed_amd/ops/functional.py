@@ -254,10 +254,11 @@ def fused_cross_entropy(logits, targets, ignore_index=-100):
 
 
 # ------------------------------------------------ ragged prefill attention
-def _ragged_prefill_torch(q, kpool, vpool, batch):
+def _ragged_prefill_torch(q, kpool, vpool, batch, window=None):
     """Plain loop over the sequences: SDPA per sequence with an explicit
     causal-offset mask (token j of a sequence sees pool positions
-    0..kv_len-q_len+j of its slot)."""
+    0..kv_len-q_len+j of its slot; under `window` only the last `window` of
+    them, itself included)."""
     T, Hq, D = q.shape
     G = Hq // kpool.shape[2]
     out = torch.empty_like(q)
@@ -271,6 +272,8 @@ def _ragged_prefill_torch(q, kpool, vpool, batch):
         pos = torch.arange(kv_len - q_len, kv_len, device=q.device)
         col = torch.arange(kv_len, device=q.device)
         mask = col.view(1, -1) <= pos.view(-1, 1)               # [q,kv]
+        if window is not None:
+            mask &= col.view(1, -1) > pos.view(-1, 1) - window
         o = torch.nn.functional.scaled_dot_product_attention(
             qs.unsqueeze(0), ks.unsqueeze(0), vs.unsqueeze(0),
             attn_mask=mask)
@@ -450,6 +453,36 @@ class _DecodeRows:
     def __init__(self, rows, lens):
         self.seqs = [(int(s), i, 1, int(n)) for i, (s, n) in
                      enumerate(zip(rows.tolist(), lens.tolist())) if n > 0]
+
+
+def ragged_decode_attention(q, kpool, vpool, rows, lens, window=None,
+                            max_len=None, mfma=False):
+    """Decode attention of q [n,1,Hq,D] (or [n,Hq,D]) over pool positions
+    [lo_i, lens[i]) of slot rows[i], lo_i = max(0, lens[i] - window) under a
+    window, else 0; returns [n,1,Hq,D]. An empty row is 0.
+
+    bf16 on the GPU with D in {64,128}: `ragged_decode` serves the shapes it
+    was built for (no window, G in 1/2/4/8) unless `mfma` asks for the new
+    kernel; `ragged_decode_gqa` serves every other G <= 32 and every window.
+    `max_len` (a host-side bound on lens) spares that kernel its one
+    device-to-host read. Anything else runs the torch loop."""
+    if window is not None and window < 1:
+        raise ValueError(f"window must be >= 1, got {window}")
+    n, Hq, D = q.shape[0], q.shape[-2], q.shape[-1]
+    G = Hq // kpool.shape[2]
+    if q.is_cuda and q.dtype == torch.bfloat16 and D in (64, 128):
+        ext = get_ext(required=True)
+        if window is None and not mfma and G in (1, 2, 4, 8):
+            return ext.ragged_decode(q.contiguous(), kpool, vpool, rows, lens)
+        if G > 32:
+            raise NotImplementedError(
+                f"ragged decode: GQA group {G} > 32 has no HIP kernel")
+        return ext.ragged_decode_gqa(q.contiguous(), kpool, vpool, rows, lens,
+                                     window or 0, max_len or 0)
+    out = _ragged_prefill_torch(q.reshape(n, Hq, D), kpool, vpool,
+                                _DecodeRows(rows, lens), window=window)
+    out[lens.to(out.device) == 0] = 0    # an empty row is defined as 0
+    return out.view(n, 1, Hq, D)
 
 
 def ragged_decode_attention_fp8(q, kpool, vpool, k_scale, v_scale, rows,

@@ -93,5 +93,5 @@ class SpatialInferenceBuilder(_PrebuiltBuilder):
 
 class RaggedOpsBuilder(_PrebuiltBuilder):
     NAME = "ragged_ops"
-    _required_syms = ("ragged_decode", "ragged_prefill",
+    _required_syms = ("ragged_decode", "ragged_decode_gqa", "ragged_prefill",
                       "ragged_rope_append")

@@ -1,5 +1,10 @@
 #!/usr/bin/env python3
-"""Decode latency: eager KV-cache loop vs hipGraph-captured step."""
+"""Decode latency: eager KV-cache loop vs hipGraph-captured step.
+
+`--kernels [--window W]`: the two slot-pool decode kernels, `ragged_decode` and
+`ragged_decode_gqa`, timed alternately with device events over G x context x
+batch; median, min..max and the K/V bytes the call must read over the median
+(bf16 pool, 2 * 2 * Hk * D bytes per attended position)."""
 import os
 import sys
 import time
@@ -8,7 +13,62 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 
+def _time_ms(fn, reps):
+    ev = [(torch.cuda.Event(enable_timing=True),
+           torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return sorted(a.elapsed_time(b) for a, b in ev)
+
+
+def kernels(window, reps=30, rounds=5):
+    from deepspeed_amd.ops.loader import get_ext
+    ext = get_ext(required=True)
+    D, Hk, dev = 128, 8, "cuda:0"
+    print("G ctx batch kernel median_ms min_ms max_ms TB/s")
+    for G in (4, 8):
+        for ctx in (512, 8192, 32768):
+            for n in (1, 8, 64):
+                g = torch.Generator(device=dev).manual_seed(ctx + n)
+                kp = torch.randn(n, ctx, Hk, D, device=dev, generator=g) \
+                    .bfloat16()
+                vp = torch.randn(n, ctx, Hk, D, device=dev, generator=g) \
+                    .bfloat16()
+                q = torch.randn(n, 1, G * Hk, D, device=dev, generator=g) \
+                    .bfloat16()
+                rows = torch.arange(n, device=dev)
+                lens = torch.full((n,), ctx, device=dev)
+                arms = {"ragged_decode_gqa": lambda: ext.ragged_decode_gqa(
+                    q, kp, vp, rows, lens, window, ctx)}
+                span = min(window, ctx) if window else ctx
+                if not window:
+                    arms["ragged_decode"] = lambda: ext.ragged_decode(
+                        q, kp, vp, rows, lens)
+                    a, b = (f().float() for f in arms.values())
+                    print(f"# G={G} ctx={ctx} n={n} max |new - old| = "
+                          f"{(a - b).abs().max().item():.3e}")
+                times = {k: [] for k in arms}
+                for f in arms.values():
+                    _time_ms(f, 5)               # warm-up
+                for _ in range(rounds):          # alternate the arms
+                    for k, f in arms.items():
+                        times[k] += _time_ms(f, reps)
+                nbytes = 2 * 2 * Hk * D * span * n
+                for k, t in times.items():
+                    t.sort()
+                    med = t[len(t) // 2]
+                    print(f"{G} {ctx} {n} {k} {med:.4f} {t[0]:.4f} "
+                          f"{t[-1]:.4f} {nbytes / med / 1e9:.3f}", flush=True)
+                del kp, vp
+
+
 def main():
+    if "--kernels" in sys.argv:
+        w = sys.argv.index("--window") if "--window" in sys.argv else None
+        return kernels(int(sys.argv[w + 1]) if w is not None else 0)
     model_name = sys.argv[1] if len(sys.argv) > 1 else "llama3-8b"
     n_tok = int(sys.argv[2]) if len(sys.argv) > 2 else 64
     import deepspeed_amd

@@ -21,6 +21,10 @@ fused_kv_append and the fp8-pool engine run back to back, SB_ROUNDS times
 (default 3) after one warm-up pass each, and the generated tok/s of both are
 printed per round and as median [min-max]. With SB_FUSED the pair is
 `fused_step=True`; otherwise the default whole-prompt engine.
+
+SB_MFMA=1 adds the `mfma_decode=True` arm in the default workload: the default
+engine (`ragged_decode`) and the one that decodes with `ragged_decode_gqa`
+run back to back, SB_ROUNDS times after one warm-up pass each.
 """
 import os
 import sys
@@ -44,6 +48,7 @@ BATCH = int(os.environ.get("SB_BATCH", 8))
 FUSED = int(os.environ.get("SB_FUSED", 0))
 FUSED_KV = int(os.environ.get("SB_FUSED_KV", 0))
 KV_FP8 = int(os.environ.get("SB_KV_FP8", 0))
+MFMA = int(os.environ.get("SB_MFMA", 0))
 ROUNDS = int(os.environ.get("SB_ROUNDS", 3))
 PROMPT = int(os.environ.get("SB_PROMPT", 256))
 CHUNK = int(os.environ.get("SB_CHUNK", 64))
@@ -128,11 +133,11 @@ def main_fused(model, dev):
             kv)[0], gtok)
 
 
-def _run_decode(model, prompts, dev, fused_kv, kv_dtype=None):
+def _run_decode(model, prompts, dev, fused_kv, kv_dtype=None, mfma=False):
     """One timed pass of the default (whole-prompt prefill) engine."""
     cb = ContinuousBatchingEngine(model, max_batch=BATCH,
                                   fused_kv_append=fused_kv,
-                                  kv_dtype=kv_dtype)
+                                  kv_dtype=kv_dtype, mfma_decode=mfma)
     if dev == "cuda":
         torch.cuda.synchronize()
     t0 = time.time()
@@ -196,6 +201,21 @@ def main():
     if KV_FP8:
         _fp8_rounds(lambda kv, warm: _run_decode(
             model, prompts[:BATCH] if warm else prompts, dev, True, kv), tok)
+    if MFMA:
+        arms = (("ragged_decode", False), ("ragged_decode_gqa", True))
+        for _, m in arms:
+            _run_decode(model, prompts[:BATCH], dev, False, mfma=m)
+        rates = {name: [] for name, _ in arms}
+        for rnd in range(ROUNDS):
+            for name, m in arms:
+                rates[name].append(
+                    tok / _run_decode(model, prompts, dev, False, mfma=m))
+            print(f"round {rnd}: " + "  ".join(
+                f"{name} {rates[name][-1]:8.1f} tok/s" for name, _ in arms))
+        for name, _ in arms:
+            r = sorted(rates[name])
+            print(f"decode {name:17s}: {r[len(r) // 2]:8.1f} tok/s median "
+                  f"[{r[0]:.1f}-{r[-1]:.1f}] over {ROUNDS} rounds")
 
 
 if __name__ == "__main__":
