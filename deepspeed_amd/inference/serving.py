@@ -29,7 +29,11 @@ index_puts of every layer by one `ragged_rope_append` HIP launch.
 keeps the pool as OCP e4m3fn codes `[B, Smax, Hk, D]` plus one fp32 scale per
 (slot, position, kv head): D + 4 bytes per cached row instead of 2 D. The
 append quantizes (`ragged_rope_append_fp8`), decode and the fused step read
-codes and scales directly (`ragged_decode_fp8`, `ragged_prefill_fp8`).
+codes and scales directly: `ragged_decode_fp8` or, for the GQA groups and
+sliding windows it does not serve and whenever `mfma_decode=True`,
+`ragged_decode_gqa_fp8` (MFMA split-KV); `ragged_prefill_fp8` on the fused
+step. A sliding window is served on the decode step of either pool; the fused
+step has none (`ragged_prefill*`).
 """
 from dataclasses import dataclass, field
 from typing import List, Optional
@@ -67,15 +71,12 @@ class RaggedKVCache:
         # window: a token attends the last `window` positions, itself
         # included (LlamaConfig.sliding_window). The pool still keeps every
         # position; decode and the masked fallbacks read the band only.
-        # mfma_decode: every decode step runs `ragged_decode_gqa`, also at
-        # the shapes `ragged_decode` serves. max_len: the engine's host-side
-        # bound on this step's lengths (spares that kernel its host read).
+        # mfma_decode: every decode step runs `ragged_decode_gqa` (fp8 pool:
+        # `ragged_decode_gqa_fp8`), also at the shapes `ragged_decode` /
+        # `ragged_decode_fp8` serve. max_len: the engine's host-side bound on
+        # this step's lengths (spares that kernel its host read).
         if window is not None and window < 1:
             raise ValueError(f"window must be >= 1, got {window}")
-        if window is not None and fp8:
-            raise NotImplementedError(
-                f"sliding_window={window} with the fp8 KV slot pool: the fp8 "
-                "ragged kernels have no window")
         self.window = window
         self.mfma_decode = mfma_decode
         self.max_len = None
@@ -288,10 +289,6 @@ class ContinuousBatchingEngine:
             raise NotImplementedError(
                 f"sliding_window={window} with fused_step=True: "
                 "ragged_prefill has no window")
-        if window is not None and self.kv_fp8:
-            raise NotImplementedError(
-                f"sliding_window={window} with kv_dtype='fp8': the fp8 "
-                "ragged kernels have no window")
         group = cfg.num_attention_heads // cfg.num_key_value_heads
         on_kernel = (torch.device(self.device).type == "cuda"
                      and dtype == torch.bfloat16
@@ -300,8 +297,9 @@ class ContinuousBatchingEngine:
             raise NotImplementedError(
                 f"fused_step=True with GQA group {group}: ragged_prefill "
                 "serves groups 1, 2, 4 and 8")
-        # mfma_decode (opt-in): every decode step runs `ragged_decode_gqa`,
-        # sized from the host-side request lengths (no device-to-host read)
+        # mfma_decode (opt-in): every decode step runs `ragged_decode_gqa`
+        # (`ragged_decode_gqa_fp8` over the fp8 pool), sized from the
+        # host-side request lengths (no device-to-host read)
         self.mfma_decode = mfma_decode
         self.caches = [RaggedKVCache(max_batch, self.max_seq,
                                      cfg.num_key_value_heads, cfg.head_dim,

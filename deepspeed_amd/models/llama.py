@@ -110,10 +110,6 @@ class LlamaAttention(nn.Module):
                 raise NotImplementedError(
                     f"sliding_window={win} with the fused serving step: "
                     "ragged_prefill has no window")
-            if getattr(kv_cache, "fp8", False):
-                raise NotImplementedError(
-                    f"sliding_window={win} with the fp8 KV slot pool: the "
-                    "fp8 ragged kernels have no window")
             if hasattr(kv_cache, "ragged") and \
                     getattr(kv_cache, "window", None) != win:
                 raise NotImplementedError(
@@ -148,7 +144,10 @@ class LlamaAttention(nn.Module):
                         q[0], kv_cache.k, kv_cache.v, kv_cache.k_scale,
                         kv_cache.v_scale, fb)
                 else:
-                    o = Fops.ragged_decode_attention_fp8(q, *rg)
+                    o = Fops.ragged_decode_attention_fp8(
+                        q, *rg, window=getattr(kv_cache, "window", None),
+                        max_len=getattr(kv_cache, "max_len", None),
+                        mfma=getattr(kv_cache, "mfma_decode", False))
             elif fb is not None:
                 # fused serving step: packed tokens of many sequences,
                 # attention straight over the slot pool

@@ -48,7 +48,8 @@ def _sources():
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 BAND_UNITS = {"attention_band.hip": "attention.hip",
               "attention_bwd_band.hip": "attention_bwd.hip"}
-NO_PACKED_UNITS = set(BAND_UNITS) | {"ragged_decode_gqa.hip"}
+NO_PACKED_UNITS = set(BAND_UNITS) | {"ragged_decode_gqa.hip",
+                                     "ragged_decode_gqa_fp8.hip"}
 
 
 def _headers_mtime():

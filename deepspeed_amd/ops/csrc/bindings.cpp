@@ -28,6 +28,11 @@ at::Tensor ragged_rope_append(at::Tensor q, at::Tensor k, at::Tensor v,
 at::Tensor ragged_decode_fp8(at::Tensor q, at::Tensor kpool, at::Tensor vpool,
                              at::Tensor k_scale, at::Tensor v_scale,
                              at::Tensor rows, at::Tensor lens, long chunk);
+at::Tensor ragged_decode_gqa_fp8(at::Tensor q, at::Tensor kpool,
+                                 at::Tensor vpool, at::Tensor k_scale,
+                                 at::Tensor v_scale, at::Tensor rows,
+                                 at::Tensor lens, long window, long max_len,
+                                 long splits);
 at::Tensor ragged_prefill_fp8(at::Tensor q, at::Tensor kpool,
                               at::Tensor vpool, at::Tensor k_scale,
                               at::Tensor v_scale, at::Tensor desc,
@@ -154,6 +159,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kpool"), py::arg("vpool"), py::arg("k_scale"),
         py::arg("v_scale"), py::arg("rows"), py::arg("lens"),
         py::arg("chunk") = 512);
+  m.def("ragged_decode_gqa_fp8", &ragged_decode_gqa_fp8, py::arg("q"),
+        py::arg("kpool"), py::arg("vpool"), py::arg("k_scale"),
+        py::arg("v_scale"), py::arg("rows"), py::arg("lens"),
+        py::arg("window") = 0, py::arg("max_len") = 0, py::arg("splits") = 0);
   m.def("ragged_prefill_fp8", &ragged_prefill_fp8, py::arg("q"),
         py::arg("kpool"), py::arg("vpool"), py::arg("k_scale"),
         py::arg("v_scale"), py::arg("desc"), py::arg("max_qlen"),

@@ -486,22 +486,38 @@ def ragged_decode_attention(q, kpool, vpool, rows, lens, window=None,
 
 
 def ragged_decode_attention_fp8(q, kpool, vpool, k_scale, v_scale, rows,
-                                lens, chunk=512):
-    """Decode attention of q [n,1,Hq,D] (or [n,Hq,D]) over the first lens[i]
-    positions of fp8 pool slot rows[i]; returns [n,1,Hq,D].
+                                lens, chunk=512, window=None, max_len=None,
+                                mfma=False):
+    """Decode attention of q [n,1,Hq,D] (or [n,Hq,D]) over pool positions
+    [lo_i, lens[i]) of fp8 pool slot rows[i], lo_i as in
+    `ragged_decode_attention`; returns [n,1,Hq,D]. An empty row is 0.
 
-    bf16 on the GPU runs the `ragged_decode_fp8` HIP kernel; anything else
-    dequantizes the pool and runs the torch loop of the prefill fallback."""
+    bf16 on the GPU: `ragged_decode_fp8` serves the shapes it was built for
+    (no window, G in 1/2/4/8) unless `mfma` asks for the new kernel;
+    `ragged_decode_gqa_fp8` serves every other G <= 32 and every window, and
+    `max_len` (a host-side bound on lens) spares it its one device-to-host
+    read. Anything else dequantizes the pool and runs the torch loop of the
+    prefill fallback."""
     _check_kv_fp8(kpool, vpool, k_scale, v_scale)
+    if window is not None and window < 1:
+        raise ValueError(f"window must be >= 1, got {window}")
+    n, Hq, D = q.shape[0], q.shape[-2], q.shape[-1]
     if q.is_cuda and q.dtype == torch.bfloat16:
         ext = get_ext(required=True)
-        return ext.ragged_decode_fp8(q.contiguous(), kpool, vpool, k_scale,
-                                     v_scale, rows, lens, chunk)
-    n, Hq, D = q.shape[0], q.shape[-2], q.shape[-1]
+        G = Hq // kpool.shape[2]
+        if window is None and not mfma and G in (1, 2, 4, 8):
+            return ext.ragged_decode_fp8(q.contiguous(), kpool, vpool,
+                                         k_scale, v_scale, rows, lens, chunk)
+        if G > 32:
+            raise NotImplementedError(
+                f"ragged decode: GQA group {G} > 32 has no HIP kernel")
+        return ext.ragged_decode_gqa_fp8(q.contiguous(), kpool, vpool,
+                                         k_scale, v_scale, rows, lens,
+                                         window or 0, max_len or 0)
     out = _ragged_prefill_torch(q.reshape(n, Hq, D),
                                 kv_dequantize(kpool, k_scale, q.dtype),
                                 kv_dequantize(vpool, v_scale, q.dtype),
-                                _DecodeRows(rows, lens))
+                                _DecodeRows(rows, lens), window=window)
     out[lens.to(out.device) == 0] = 0    # an empty row is defined as 0
     return out.view(n, 1, Hq, D)
 

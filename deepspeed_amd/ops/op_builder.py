@@ -93,5 +93,6 @@ class SpatialInferenceBuilder(_PrebuiltBuilder):
 
 class RaggedOpsBuilder(_PrebuiltBuilder):
     NAME = "ragged_ops"
-    _required_syms = ("ragged_decode", "ragged_decode_gqa", "ragged_prefill",
+    _required_syms = ("ragged_decode", "ragged_decode_gqa",
+                      "ragged_decode_gqa_fp8", "ragged_prefill",
                       "ragged_rope_append")

@@ -4,7 +4,12 @@
 `--kernels [--window W]`: the two slot-pool decode kernels, `ragged_decode` and
 `ragged_decode_gqa`, timed alternately with device events over G x context x
 batch; median, min..max and the K/V bytes the call must read over the median
-(bf16 pool, 2 * 2 * Hk * D bytes per attended position)."""
+(bf16 pool, 2 * 2 * Hk * D bytes per attended position).
+
+`--kernels --fp8 [--window W]`: the same over pools made with `kv_quantize`:
+`ragged_decode_fp8` (no window only) and `ragged_decode_gqa_fp8`, 2 * Hk *
+(D + 4) bytes per attended position, with `ragged_decode_gqa` on the bf16 pool
+of the same shape as the yardstick."""
 import os
 import sys
 import time
@@ -24,7 +29,7 @@ def _time_ms(fn, reps):
     return sorted(a.elapsed_time(b) for a, b in ev)
 
 
-def kernels(window, reps=30, rounds=5):
+def kernels(window, fp8=False, reps=30, rounds=5):
     from deepspeed_amd.ops.loader import get_ext
     ext = get_ext(required=True)
     D, Hk, dev = 128, 8, "cuda:0"
@@ -44,7 +49,26 @@ def kernels(window, reps=30, rounds=5):
                 arms = {"ragged_decode_gqa": lambda: ext.ragged_decode_gqa(
                     q, kp, vp, rows, lens, window, ctx)}
                 span = min(window, ctx) if window else ctx
-                if not window:
+                nbytes = {"ragged_decode_gqa": 2 * 2 * Hk * D * span * n}
+                if fp8:
+                    from deepspeed_amd.ops.functional import kv_quantize
+                    (kc, ks), (vc, vs) = kv_quantize(kp), kv_quantize(vp)
+                    arms["ragged_decode_gqa_fp8"] = \
+                        lambda: ext.ragged_decode_gqa_fp8(
+                            q, kc, vc, ks, vs, rows, lens, window, ctx)
+                    if not window:
+                        arms["ragged_decode_fp8"] = \
+                            lambda: ext.ragged_decode_fp8(q, kc, vc, ks, vs,
+                                                          rows, lens)
+                    for k in list(arms)[1:]:
+                        nbytes[k] = 2 * Hk * (D + 4) * span * n
+                    new = arms["ragged_decode_gqa_fp8"]().float()
+                    for k, f in arms.items():
+                        if k != "ragged_decode_gqa_fp8":
+                            d = (new - f().float()).abs().max().item()
+                            print(f"# G={G} ctx={ctx} n={n} max |gqa_fp8 - "
+                                  f"{k}| = {d:.3e}")
+                elif not window:
                     arms["ragged_decode"] = lambda: ext.ragged_decode(
                         q, kp, vp, rows, lens)
                     a, b = (f().float() for f in arms.values())
@@ -56,19 +80,20 @@ def kernels(window, reps=30, rounds=5):
                 for _ in range(rounds):          # alternate the arms
                     for k, f in arms.items():
                         times[k] += _time_ms(f, reps)
-                nbytes = 2 * 2 * Hk * D * span * n
                 for k, t in times.items():
                     t.sort()
                     med = t[len(t) // 2]
+                    nb = nbytes.get(k, nbytes["ragged_decode_gqa"])
                     print(f"{G} {ctx} {n} {k} {med:.4f} {t[0]:.4f} "
-                          f"{t[-1]:.4f} {nbytes / med / 1e9:.3f}", flush=True)
-                del kp, vp
+                          f"{t[-1]:.4f} {nb / med / 1e9:.3f}", flush=True)
+                del kp, vp, arms
 
 
 def main():
     if "--kernels" in sys.argv:
         w = sys.argv.index("--window") if "--window" in sys.argv else None
-        return kernels(int(sys.argv[w + 1]) if w is not None else 0)
+        return kernels(int(sys.argv[w + 1]) if w is not None else 0,
+                       fp8="--fp8" in sys.argv)
     model_name = sys.argv[1] if len(sys.argv) > 1 else "llama3-8b"
     n_tok = int(sys.argv[2]) if len(sys.argv) > 2 else 64
     import deepspeed_amd
