@@ -19,7 +19,10 @@ GQA groups and sliding windows `ragged_decode` does not serve and whenever
 `fused_step=True` (opt-in) is Dynamic SplitFuse proper: every step packs
 its prefill chunks and one token per decoding request into ONE ragged
 model call, described by a `RaggedBatch` and served by the
-`ragged_prefill` HIP kernel, so the weights are read once per step.
+`ragged_prefill` HIP kernel, so the weights are read once per step. On the
+bf16 pool `ragged_prefill_gqa` (MFMA, (token, head) columns) serves the GQA
+groups up to 32 and the sliding windows `ragged_prefill` does not, and every
+fused step when `mfma_prefill=True`.
 
 `fused_kv_append=True` (opt-in) replaces, on the fused step and on the
 batched decode step, the eager per-row RoPE of q and k and the pool / length
@@ -32,8 +35,9 @@ append quantizes (`ragged_rope_append_fp8`), decode and the fused step read
 codes and scales directly: `ragged_decode_fp8` or, for the GQA groups and
 sliding windows it does not serve and whenever `mfma_decode=True`,
 `ragged_decode_gqa_fp8` (MFMA split-KV); `ragged_prefill_fp8` on the fused
-step. A sliding window is served on the decode step of either pool; the fused
-step has none (`ragged_prefill*`).
+step. A sliding window is served on the decode step of either pool and on the
+fused step of the bf16 pool; the fused step over the fp8 pool has none and
+keeps its group list (`ragged_prefill_fp8`).
 """
 from dataclasses import dataclass, field
 from typing import List, Optional
@@ -67,18 +71,23 @@ class RaggedKVCache:
     """One layer's slot-granular KV pool with per-slot lengths."""
 
     def __init__(self, max_batch, max_seq, n_kv, d, dtype, device,
-                 rope=None, fp8=False, window=None, mfma_decode=False):
+                 rope=None, fp8=False, window=None, mfma_decode=False,
+                 mfma_prefill=False):
         # window: a token attends the last `window` positions, itself
         # included (LlamaConfig.sliding_window). The pool still keeps every
-        # position; decode and the masked fallbacks read the band only.
+        # position; decode, the fused step and the masked fallbacks read the
+        # band only.
         # mfma_decode: every decode step runs `ragged_decode_gqa` (fp8 pool:
         # `ragged_decode_gqa_fp8`), also at the shapes `ragged_decode` /
         # `ragged_decode_fp8` serve. max_len: the engine's host-side bound on
         # this step's lengths (spares that kernel its host read).
+        # mfma_prefill: every fused step on the bf16 pool runs
+        # `ragged_prefill_gqa`, also at the shapes `ragged_prefill` serves.
         if window is not None and window < 1:
             raise ValueError(f"window must be >= 1, got {window}")
         self.window = window
         self.mfma_decode = mfma_decode
+        self.mfma_prefill = mfma_prefill
         self.max_len = None
         # fp8: e4m3fn codes plus one fp32 scale per (slot, position, kv head)
         # row -- ops.functional.kv_quantize. Needs `rope` (every ragged step
@@ -247,7 +256,8 @@ class ContinuousBatchingEngine:
 
     def __init__(self, model, max_batch=8, max_seq=None, device=None,
                  prefill_chunk=None, prefill_budget=None, fused_step=False,
-                 fused_kv_append=False, kv_dtype=None, mfma_decode=False):
+                 fused_kv_append=False, kv_dtype=None, mfma_decode=False,
+                 mfma_prefill=False):
         self.model = model
         cfg = model.cfg if hasattr(model, "cfg") else model.config
         self.cfg = cfg
@@ -282,30 +292,42 @@ class ContinuousBatchingEngine:
         self.kv_fp8 = kv_dtype is not None
         if self.kv_fp8 and not fused_kv_append:
             raise ValueError("kv_dtype='fp8' needs fused_kv_append=True")
-        # sliding_window models: the decode step and the masked fallbacks
-        # attend the band; the steps without a window kernel are refused here
+        # sliding_window models: the decode step, the fused step on the bf16
+        # pool and the masked fallbacks attend the band; the one step without
+        # a window kernel is refused here
         window = getattr(cfg, "sliding_window", None)
-        if window is not None and fused_step:
+        if window is not None and fused_step and self.kv_fp8:
             raise NotImplementedError(
-                f"sliding_window={window} with fused_step=True: "
-                "ragged_prefill has no window")
+                f"sliding_window={window} with fused_step=True and "
+                "kv_dtype='fp8': ragged_prefill_fp8 has no window")
         group = cfg.num_attention_heads // cfg.num_key_value_heads
         on_kernel = (torch.device(self.device).type == "cuda"
                      and dtype == torch.bfloat16
                      and cfg.head_dim in (64, 128))
-        if fused_step and on_kernel and group not in (1, 2, 4, 8):
-            raise NotImplementedError(
-                f"fused_step=True with GQA group {group}: ragged_prefill "
-                "serves groups 1, 2, 4 and 8")
+        if fused_step and on_kernel:
+            if self.kv_fp8 and group not in (1, 2, 4, 8):
+                raise NotImplementedError(
+                    f"fused_step=True with GQA group {group} and "
+                    "kv_dtype='fp8': ragged_prefill_fp8 serves groups 1, 2, "
+                    "4 and 8")
+            if group > 32:
+                raise NotImplementedError(
+                    f"fused_step=True with GQA group {group}: "
+                    "ragged_prefill_gqa serves groups up to 32")
         # mfma_decode (opt-in): every decode step runs `ragged_decode_gqa`
         # (`ragged_decode_gqa_fp8` over the fp8 pool), sized from the
         # host-side request lengths (no device-to-host read)
         self.mfma_decode = mfma_decode
+        # mfma_prefill (opt-in): every fused step on the bf16 pool runs
+        # `ragged_prefill_gqa`; by default it serves the groups and windows
+        # `ragged_prefill` does not
+        self.mfma_prefill = mfma_prefill
         self.caches = [RaggedKVCache(max_batch, self.max_seq,
                                      cfg.num_key_value_heads, cfg.head_dim,
                                      dtype, self.device, rope=rope,
                                      fp8=self.kv_fp8, window=window,
-                                     mfma_decode=mfma_decode)
+                                     mfma_decode=mfma_decode,
+                                     mfma_prefill=mfma_prefill)
                        for _ in range(cfg.num_hidden_layers)]
         # Dynamic SplitFuse-style scheduling (ref FastGen): bound the
         # prompt tokens processed per step so long prompts stream in

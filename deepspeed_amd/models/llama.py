@@ -106,10 +106,11 @@ class LlamaAttention(nn.Module):
         wkw = {} if win is None else {"window": win}
         if win is not None and kv_cache is not None:
             # the slot-pool steps that would attend the whole context
-            if getattr(kv_cache, "fused", None) is not None:
+            if getattr(kv_cache, "fused", None) is not None and \
+                    getattr(kv_cache, "fp8", False):
                 raise NotImplementedError(
-                    f"sliding_window={win} with the fused serving step: "
-                    "ragged_prefill has no window")
+                    f"sliding_window={win} with the fused serving step over "
+                    "the fp8 pool: ragged_prefill_fp8 has no window")
             if hasattr(kv_cache, "ragged") and \
                     getattr(kv_cache, "window", None) != win:
                 raise NotImplementedError(
@@ -150,10 +151,16 @@ class LlamaAttention(nn.Module):
                         mfma=getattr(kv_cache, "mfma_decode", False))
             elif fb is not None:
                 # fused serving step: packed tokens of many sequences,
-                # attention straight over the slot pool
+                # attention straight over the slot pool, over the cache's
+                # window
                 from ..ops.functional import ragged_prefill_attention
+                fkw = {}
+                if getattr(kv_cache, "window", None) is not None:
+                    fkw["window"] = kv_cache.window
+                if getattr(kv_cache, "mfma_prefill", False):
+                    fkw["mfma"] = True
                 o = ragged_prefill_attention(q[0], kv_cache.k, kv_cache.v,
-                                             fb)
+                                             fb, **fkw)
             elif rg is not None:
                 # ragged decode straight from the slot pool (no copies),
                 # over the cache's window

@@ -49,7 +49,8 @@ NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 BAND_UNITS = {"attention_band.hip": "attention.hip",
               "attention_bwd_band.hip": "attention_bwd.hip"}
 NO_PACKED_UNITS = set(BAND_UNITS) | {"ragged_decode_gqa.hip",
-                                     "ragged_decode_gqa_fp8.hip"}
+                                     "ragged_decode_gqa_fp8.hip",
+                                     "ragged_prefill_gqa.hip"}
 
 
 def _headers_mtime():

@@ -20,6 +20,9 @@ at::Tensor ragged_decode_gqa(at::Tensor q, at::Tensor kpool, at::Tensor vpool,
                              long max_len, long splits);
 at::Tensor ragged_prefill(at::Tensor q, at::Tensor kpool, at::Tensor vpool,
                           at::Tensor desc, long max_qlen, long max_kvlen);
+at::Tensor ragged_prefill_gqa(at::Tensor q, at::Tensor kpool,
+                              at::Tensor vpool, at::Tensor desc, long max_qlen,
+                              long max_kvlen, long window);
 at::Tensor ragged_rope_append(at::Tensor q, at::Tensor k, at::Tensor v,
                               at::Tensor cos, at::Tensor sin,
                               at::Tensor tok_slot, at::Tensor tok_pos,
@@ -151,6 +154,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ragged_prefill", &ragged_prefill, py::arg("q"), py::arg("kpool"),
         py::arg("vpool"), py::arg("desc"), py::arg("max_qlen"),
         py::arg("max_kvlen"));
+  m.def("ragged_prefill_gqa", &ragged_prefill_gqa, py::arg("q"),
+        py::arg("kpool"), py::arg("vpool"), py::arg("desc"),
+        py::arg("max_qlen"), py::arg("max_kvlen"), py::arg("window") = 0);
   m.def("ragged_rope_append", &ragged_rope_append, py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("cos"), py::arg("sin"),
         py::arg("tok_slot"), py::arg("tok_pos"), py::arg("kpool"),

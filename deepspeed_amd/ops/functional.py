@@ -281,19 +281,35 @@ def _ragged_prefill_torch(q, kpool, vpool, batch, window=None):
     return out
 
 
-def ragged_prefill_attention(q, kpool, vpool, batch):
+def ragged_prefill_attention(q, kpool, vpool, batch, window=None,
+                             mfma=False):
     """Attention of one ragged serving step straight over the KV slot pool.
 
     q [T,Hq,D] packed tokens of all sequences in `batch` (a RaggedBatch),
     kpool/vpool [B,Smax,Hk,D] with this step's K/V rows already written.
-    Returns [T,Hq,D]. bf16 on the GPU with D in {64,128} runs the
-    `ragged_prefill` HIP kernel (no host sync); anything else the torch loop.
-    """
+    Returns [T,Hq,D]. Under `window` a token sees its last `window`
+    positions, itself included.
+
+    bf16 on the GPU with D in {64,128} (no host sync): `ragged_prefill` serves
+    the shapes it was built for (no window, G in 1/2/4/8) unless `mfma` asks
+    for the new kernel; `ragged_prefill_gqa` serves every other G <= 32 and
+    every window. Anything else runs the torch loop."""
+    if window is not None and window < 1:
+        raise ValueError(f"window must be >= 1, got {window}")
+    G = q.shape[1] // kpool.shape[2]
     if q.is_cuda and q.dtype == torch.bfloat16 and q.shape[-1] in (64, 128):
         ext = get_ext(required=True)
-        return ext.ragged_prefill(q.contiguous(), kpool, vpool, batch.desc,
-                                  batch.max_qlen, batch.max_kvlen)
-    return _ragged_prefill_torch(q, kpool, vpool, batch)
+        if window is None and not mfma and G in (1, 2, 4, 8):
+            return ext.ragged_prefill(q.contiguous(), kpool, vpool,
+                                      batch.desc, batch.max_qlen,
+                                      batch.max_kvlen)
+        if G > 32:
+            raise NotImplementedError(
+                f"ragged prefill: GQA group {G} > 32 has no HIP kernel")
+        return ext.ragged_prefill_gqa(q.contiguous(), kpool, vpool,
+                                      batch.desc, batch.max_qlen,
+                                      batch.max_kvlen, window or 0)
+    return _ragged_prefill_torch(q, kpool, vpool, batch, window=window)
 
 
 # --------------------------------------------- ragged RoPE + KV append

@@ -9,7 +9,13 @@ batch; median, min..max and the K/V bytes the call must read over the median
 `--kernels --fp8 [--window W]`: the same over pools made with `kv_quantize`:
 `ragged_decode_fp8` (no window only) and `ragged_decode_gqa_fp8`, 2 * Hk *
 (D + 4) bytes per attended position, with `ragged_decode_gqa` on the bf16 pool
-of the same shape as the yardstick."""
+of the same shape as the yardstick.
+
+`--prefill-kernels`: the two fused-step kernels, `ragged_prefill` and
+`ragged_prefill_gqa`, the same way over a decode-only step (64 rows at context
+8192), a chunk step (8 x 256 new tokens over a 4096-token prefix), both mixed,
+and the chunk step with window 4096 at prefix 32768 (new kernel only);
+8 kv heads, D 128, G 4, 8 and 7 (new kernel only)."""
 import os
 import sys
 import time
@@ -89,7 +95,55 @@ def kernels(window, fp8=False, reps=30, rounds=5):
                 del kp, vp, arms
 
 
+def prefill_kernels(reps=20, rounds=3):
+    """The fused-step kernels, `ragged_prefill` (G 4 and 8, no window) and
+    `ragged_prefill_gqa`, alternately over the same ragged steps."""
+    from deepspeed_amd.inference.ragged_batch import RaggedBatch
+    from deepspeed_amd.ops.loader import get_ext
+    ext = get_ext(required=True)
+    D, Hk, dev = 128, 8, "cuda:0"
+    dec = [(1, 8192)] * 64
+    chunk = [(256, 4096 + 256)] * 8
+    steps = (("decode", dec, 0), ("chunk", chunk, 0),
+             ("mixed", dec + chunk, 0),
+             ("chunk_w4096", [(256, 32768 + 256)] * 8, 4096))
+    print("G step kernel median_ms min_ms max_ms")
+    for name, pairs, window in steps:
+        n, smax = len(pairs), max(kv for _, kv in pairs)
+        g = torch.Generator(device=dev).manual_seed(n + smax)
+        kp = torch.randn(n, smax, Hk, D, device=dev, generator=g).bfloat16()
+        vp = torch.randn(n, smax, Hk, D, device=dev, generator=g).bfloat16()
+        seqs, t = [], 0
+        for slot, (ql, kv) in enumerate(pairs):
+            seqs.append((slot, t, ql, kv))
+            t += ql
+        b = RaggedBatch(seqs, n, smax, dev)
+        for G in ((4, 8) if window else (4, 8, 7)):
+            q = torch.randn(t, G * Hk, D, device=dev, generator=g).bfloat16()
+            arms = {"ragged_prefill_gqa": lambda: ext.ragged_prefill_gqa(
+                q, kp, vp, b.desc, b.max_qlen, b.max_kvlen, window)}
+            if not window and G != 7:
+                arms["ragged_prefill"] = lambda: ext.ragged_prefill(
+                    q, kp, vp, b.desc, b.max_qlen, b.max_kvlen)
+                x, y = (f().float() for f in arms.values())
+                print(f"# G={G} {name} max |new - old| = "
+                      f"{(x - y).abs().max().item():.3e}")
+            times = {k: [] for k in arms}
+            for f in arms.values():
+                _time_ms(f, 5)                   # warm-up
+            for _ in range(rounds):              # alternate the arms
+                for k, f in arms.items():
+                    times[k] += _time_ms(f, reps)
+            for k, ts in times.items():
+                ts.sort()
+                print(f"{G} {name} {k} {ts[len(ts) // 2]:.4f} {ts[0]:.4f} "
+                      f"{ts[-1]:.4f}", flush=True)
+        del kp, vp
+
+
 def main():
+    if "--prefill-kernels" in sys.argv:
+        return prefill_kernels()
     if "--kernels" in sys.argv:
         w = sys.argv.index("--window") if "--window" in sys.argv else None
         return kernels(int(sys.argv[w + 1]) if w is not None else 0,

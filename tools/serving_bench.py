@@ -25,6 +25,12 @@ printed per round and as median [min-max]. With SB_FUSED the pair is
 SB_MFMA=1 adds the `mfma_decode=True` arm in the default workload: the default
 engine (`ragged_decode`) and the one that decodes with `ragged_decode_gqa`
 run back to back, SB_ROUNDS times after one warm-up pass each.
+
+`--mfma-prefill` runs only the fused-step pair: `fused_step=True,
+fused_kv_append=True` with `mfma_prefill` off (`ragged_prefill`) and on
+(`ragged_prefill_gqa`) back to back, SB_ROUNDS times after one warm-up pass
+each, over the default workload's prompts or, with SB_FUSED=1, the prompt-heavy
+ones.
 """
 import os
 import sys
@@ -77,7 +83,8 @@ def _fp8_rounds(run, gtok):
           f"{med['fp8 pool'] / med['bf16 pool']:.2f}x")
 
 
-def _run_budgeted(model, prompts, fused, dev, fused_kv=False, kv_dtype=None):
+def _run_budgeted(model, prompts, fused, dev, fused_kv=False, kv_dtype=None,
+                  mfma_prefill=False):
     """One timed pass; returns (seconds, model forwards, engine steps)."""
     calls = [0]
     hook = model.register_forward_hook(
@@ -85,7 +92,8 @@ def _run_budgeted(model, prompts, fused, dev, fused_kv=False, kv_dtype=None):
     cb = ContinuousBatchingEngine(model, max_batch=BATCH,
                                   prefill_chunk=CHUNK, prefill_budget=BUDGET,
                                   fused_step=fused, fused_kv_append=fused_kv,
-                                  kv_dtype=kv_dtype)
+                                  kv_dtype=kv_dtype,
+                                  mfma_prefill=mfma_prefill)
     for p in prompts:
         cb.add_request(p, max_new_tokens=NEW)
     if dev == "cuda":
@@ -133,6 +141,24 @@ def main_fused(model, dev):
             kv)[0], gtok)
 
 
+def main_mfma_prefill(model, prompts, dev):
+    gtok = len(prompts) * NEW
+    arms = (("ragged_prefill", False), ("ragged_prefill_gqa", True))
+    for _, m in arms:
+        _run_budgeted(model, prompts[:BATCH], True, dev, True, mfma_prefill=m)
+    rates = {name: [] for name, _ in arms}
+    for rnd in range(ROUNDS):
+        for name, m in arms:
+            rates[name].append(gtok / _run_budgeted(
+                model, prompts, True, dev, True, mfma_prefill=m)[0])
+        print(f"round {rnd}: " + "  ".join(
+            f"{name} {rates[name][-1]:8.1f} tok/s" for name, _ in arms))
+    for name, _ in arms:
+        r = sorted(rates[name])
+        print(f"fused step {name:18s}: {r[len(r) // 2]:8.1f} generated tok/s "
+              f"median [{r[0]:.1f}-{r[-1]:.1f}] over {ROUNDS} rounds")
+
+
 def _run_decode(model, prompts, dev, fused_kv, kv_dtype=None, mfma=False):
     """One timed pass of the default (whole-prompt prefill) engine."""
     cb = ContinuousBatchingEngine(model, max_batch=BATCH,
@@ -156,9 +182,17 @@ def main():
     dev = "cuda" if torch.cuda.is_available() else "cpu"
     dtype = torch.bfloat16 if dev == "cuda" else torch.float32
     model = LlamaForCausalLM(LLAMA_CONFIGS[MODEL]).to(dev, dtype).eval()
+    vocab = model.cfg.vocab_size
+    if "--mfma-prefill" in sys.argv:
+        lens = [PROMPT + (i % 4) * 64 if FUSED else 32 + (i % 5) * 16
+                for i in range(NREQ)]
+        print(f"{MODEL}: {NREQ} reqs, prompts {min(lens)}..{max(lens)} + "
+              f"{NEW} new tokens each; batch {BATCH}, chunk {CHUNK}, budget "
+              f"{BUDGET}")
+        return main_mfma_prefill(
+            model, [torch.randint(0, vocab, (n,)) for n in lens], dev)
     if FUSED:
         return main_fused(model, dev)
-    vocab = model.cfg.vocab_size
     prompts = [torch.randint(0, vocab, (32 + (i % 5) * 16,))
                for i in range(NREQ)]
 
