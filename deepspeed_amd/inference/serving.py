@@ -19,10 +19,10 @@ GQA groups and sliding windows `ragged_decode` does not serve and whenever
 `fused_step=True` (opt-in) is Dynamic SplitFuse proper: every step packs
 its prefill chunks and one token per decoding request into ONE ragged
 model call, described by a `RaggedBatch` and served by the
-`ragged_prefill` HIP kernel, so the weights are read once per step. On the
-bf16 pool `ragged_prefill_gqa` (MFMA, (token, head) columns) serves the GQA
-groups up to 32 and the sliding windows `ragged_prefill` does not, and every
-fused step when `mfma_prefill=True`.
+`ragged_prefill` HIP kernel, so the weights are read once per step.
+`ragged_prefill_gqa` (MFMA, (token, head) columns) serves the GQA groups up
+to 32 and the sliding windows `ragged_prefill` does not, and every fused step
+when `mfma_prefill=True`.
 
 `fused_kv_append=True` (opt-in) replaces, on the fused step and on the
 batched decode step, the eager per-row RoPE of q and k and the pool / length
@@ -34,10 +34,11 @@ keeps the pool as OCP e4m3fn codes `[B, Smax, Hk, D]` plus one fp32 scale per
 append quantizes (`ragged_rope_append_fp8`), decode and the fused step read
 codes and scales directly: `ragged_decode_fp8` or, for the GQA groups and
 sliding windows it does not serve and whenever `mfma_decode=True`,
-`ragged_decode_gqa_fp8` (MFMA split-KV); `ragged_prefill_fp8` on the fused
-step. A sliding window is served on the decode step of either pool and on the
-fused step of the bf16 pool; the fused step over the fp8 pool has none and
-keeps its group list (`ragged_prefill_fp8`).
+`ragged_decode_gqa_fp8` (MFMA split-KV); on the fused step
+`ragged_prefill_fp8` or, in the same cases and whenever `mfma_prefill=True`,
+`ragged_prefill_gqa_fp8`. A sliding window is served on both steps of either
+pool; only off the kernels (CPU, fp32) the fused step over the fp8 pool has no
+window and is refused.
 """
 from dataclasses import dataclass, field
 from typing import List, Optional
@@ -81,8 +82,9 @@ class RaggedKVCache:
         # `ragged_decode_gqa_fp8`), also at the shapes `ragged_decode` /
         # `ragged_decode_fp8` serve. max_len: the engine's host-side bound on
         # this step's lengths (spares that kernel its host read).
-        # mfma_prefill: every fused step on the bf16 pool runs
-        # `ragged_prefill_gqa`, also at the shapes `ragged_prefill` serves.
+        # mfma_prefill: every fused step runs `ragged_prefill_gqa` (fp8 pool:
+        # `ragged_prefill_gqa_fp8`), also at the shapes `ragged_prefill` /
+        # `ragged_prefill_fp8` serve.
         if window is not None and window < 1:
             raise ValueError(f"window must be >= 1, got {window}")
         self.window = window
@@ -292,35 +294,34 @@ class ContinuousBatchingEngine:
         self.kv_fp8 = kv_dtype is not None
         if self.kv_fp8 and not fused_kv_append:
             raise ValueError("kv_dtype='fp8' needs fused_kv_append=True")
-        # sliding_window models: the decode step, the fused step on the bf16
-        # pool and the masked fallbacks attend the band; the one step without
-        # a window kernel is refused here
+        # sliding_window models: the decode step, the fused step and the
+        # masked fallbacks attend the band; the one step still refused is the
+        # fused step over the fp8 pool off the kernels (CPU, fp32)
         window = getattr(cfg, "sliding_window", None)
-        if window is not None and fused_step and self.kv_fp8:
-            raise NotImplementedError(
-                f"sliding_window={window} with fused_step=True and "
-                "kv_dtype='fp8': ragged_prefill_fp8 has no window")
         group = cfg.num_attention_heads // cfg.num_key_value_heads
         on_kernel = (torch.device(self.device).type == "cuda"
                      and dtype == torch.bfloat16
                      and cfg.head_dim in (64, 128))
-        if fused_step and on_kernel:
-            if self.kv_fp8 and group not in (1, 2, 4, 8):
-                raise NotImplementedError(
-                    f"fused_step=True with GQA group {group} and "
-                    "kv_dtype='fp8': ragged_prefill_fp8 serves groups 1, 2, "
-                    "4 and 8")
-            if group > 32:
-                raise NotImplementedError(
-                    f"fused_step=True with GQA group {group}: "
-                    "ragged_prefill_gqa serves groups up to 32")
+        if window is not None and fused_step and self.kv_fp8 \
+                and not on_kernel:
+            raise NotImplementedError(
+                f"sliding_window={window} with fused_step=True and "
+                "kv_dtype='fp8': only the HIP kernel "
+                "(ragged_prefill_gqa_fp8: cuda, bf16, head_dim 64/128) "
+                "serves a window")
+        if fused_step and on_kernel and group > 32:
+            raise NotImplementedError(
+                f"fused_step=True with GQA group {group}: "
+                "ragged_prefill_gqa and ragged_prefill_gqa_fp8 serve groups "
+                "up to 32")
         # mfma_decode (opt-in): every decode step runs `ragged_decode_gqa`
         # (`ragged_decode_gqa_fp8` over the fp8 pool), sized from the
         # host-side request lengths (no device-to-host read)
         self.mfma_decode = mfma_decode
-        # mfma_prefill (opt-in): every fused step on the bf16 pool runs
-        # `ragged_prefill_gqa`; by default it serves the groups and windows
-        # `ragged_prefill` does not
+        # mfma_prefill (opt-in): every fused step runs `ragged_prefill_gqa`
+        # (`ragged_prefill_gqa_fp8` over the fp8 pool); by default they serve
+        # the groups and windows `ragged_prefill` / `ragged_prefill_fp8` do
+        # not
         self.mfma_prefill = mfma_prefill
         self.caches = [RaggedKVCache(max_batch, self.max_seq,
                                      cfg.num_key_value_heads, cfg.head_dim,

@@ -105,12 +105,7 @@ class LlamaAttention(nn.Module):
         win = getattr(self.cfg, "sliding_window", None)
         wkw = {} if win is None else {"window": win}
         if win is not None and kv_cache is not None:
-            # the slot-pool steps that would attend the whole context
-            if getattr(kv_cache, "fused", None) is not None and \
-                    getattr(kv_cache, "fp8", False):
-                raise NotImplementedError(
-                    f"sliding_window={win} with the fused serving step over "
-                    "the fp8 pool: ragged_prefill_fp8 has no window")
+            # a slot-pool step that would attend the whole context
             if hasattr(kv_cache, "ragged") and \
                     getattr(kv_cache, "window", None) != win:
                 raise NotImplementedError(
@@ -143,7 +138,9 @@ class LlamaAttention(nn.Module):
                 if fb is not None:
                     o = Fops.ragged_prefill_attention_fp8(
                         q[0], kv_cache.k, kv_cache.v, kv_cache.k_scale,
-                        kv_cache.v_scale, fb)
+                        kv_cache.v_scale, fb,
+                        window=getattr(kv_cache, "window", None),
+                        mfma=getattr(kv_cache, "mfma_prefill", False))
                 else:
                     o = Fops.ragged_decode_attention_fp8(
                         q, *rg, window=getattr(kv_cache, "window", None),

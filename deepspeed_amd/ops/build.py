@@ -50,7 +50,8 @@ BAND_UNITS = {"attention_band.hip": "attention.hip",
               "attention_bwd_band.hip": "attention_bwd.hip"}
 NO_PACKED_UNITS = set(BAND_UNITS) | {"ragged_decode_gqa.hip",
                                      "ragged_decode_gqa_fp8.hip",
-                                     "ragged_prefill_gqa.hip"}
+                                     "ragged_prefill_gqa.hip",
+                                     "ragged_prefill_gqa_fp8.hip"}
 
 
 def _headers_mtime():

@@ -40,6 +40,10 @@ at::Tensor ragged_prefill_fp8(at::Tensor q, at::Tensor kpool,
                               at::Tensor vpool, at::Tensor k_scale,
                               at::Tensor v_scale, at::Tensor desc,
                               long max_qlen, long max_kvlen);
+at::Tensor ragged_prefill_gqa_fp8(at::Tensor q, at::Tensor kpool,
+                                  at::Tensor vpool, at::Tensor k_scale,
+                                  at::Tensor v_scale, at::Tensor desc,
+                                  long max_qlen, long max_kvlen, long window);
 at::Tensor ragged_rope_append_fp8(at::Tensor q, at::Tensor k, at::Tensor v,
                                   at::Tensor cos, at::Tensor sin,
                                   at::Tensor tok_slot, at::Tensor tok_pos,
@@ -173,6 +177,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kpool"), py::arg("vpool"), py::arg("k_scale"),
         py::arg("v_scale"), py::arg("desc"), py::arg("max_qlen"),
         py::arg("max_kvlen"));
+  m.def("ragged_prefill_gqa_fp8", &ragged_prefill_gqa_fp8, py::arg("q"),
+        py::arg("kpool"), py::arg("vpool"), py::arg("k_scale"),
+        py::arg("v_scale"), py::arg("desc"), py::arg("max_qlen"),
+        py::arg("max_kvlen"), py::arg("window") = 0);
   m.def("ragged_rope_append_fp8", &ragged_rope_append_fp8, py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("cos"), py::arg("sin"),
         py::arg("tok_slot"), py::arg("tok_pos"), py::arg("kpool"),

@@ -538,21 +538,36 @@ def ragged_decode_attention_fp8(q, kpool, vpool, k_scale, v_scale, rows,
     return out.view(n, 1, Hq, D)
 
 
-def ragged_prefill_attention_fp8(q, kpool, vpool, k_scale, v_scale, batch):
+def ragged_prefill_attention_fp8(q, kpool, vpool, k_scale, v_scale, batch,
+                                 window=None, mfma=False):
     """`ragged_prefill_attention` over the fp8 KV slot pool (this step's rows
-    already appended as codes plus scales). Returns [T,Hq,D].
+    already appended as codes plus scales). Returns [T,Hq,D]. Under `window`
+    a token sees its last `window` positions, itself included.
 
-    bf16 on the GPU runs the `ragged_prefill_fp8` HIP kernel; anything else
-    dequantizes the pool and runs the torch loop."""
+    bf16 on the GPU (no host sync): `ragged_prefill_fp8` serves the shapes it
+    was built for (no window, G in 1/2/4/8) unless `mfma` asks for the new
+    kernel; `ragged_prefill_gqa_fp8` serves every other G <= 32 and every
+    window. Anything else dequantizes the pool and runs the torch loop."""
     _check_kv_fp8(kpool, vpool, k_scale, v_scale)
+    if window is not None and window < 1:
+        raise ValueError(f"window must be >= 1, got {window}")
     if q.is_cuda and q.dtype == torch.bfloat16:
         ext = get_ext(required=True)
-        return ext.ragged_prefill_fp8(q.contiguous(), kpool, vpool, k_scale,
-                                      v_scale, batch.desc, batch.max_qlen,
-                                      batch.max_kvlen)
+        G = q.shape[1] // kpool.shape[2]
+        if window is None and not mfma and G in (1, 2, 4, 8):
+            return ext.ragged_prefill_fp8(q.contiguous(), kpool, vpool,
+                                          k_scale, v_scale, batch.desc,
+                                          batch.max_qlen, batch.max_kvlen)
+        if G > 32:
+            raise NotImplementedError(
+                f"ragged prefill: GQA group {G} > 32 has no HIP kernel")
+        return ext.ragged_prefill_gqa_fp8(q.contiguous(), kpool, vpool,
+                                          k_scale, v_scale, batch.desc,
+                                          batch.max_qlen, batch.max_kvlen,
+                                          window or 0)
     return _ragged_prefill_torch(q, kv_dequantize(kpool, k_scale, q.dtype),
                                  kv_dequantize(vpool, v_scale, q.dtype),
-                                 batch)
+                                 batch, window=window)
 
 
 def gds_handle(*a, **kw):

@@ -95,4 +95,5 @@ class RaggedOpsBuilder(_PrebuiltBuilder):
     NAME = "ragged_ops"
     _required_syms = ("ragged_decode", "ragged_decode_gqa",
                       "ragged_decode_gqa_fp8", "ragged_prefill",
-                      "ragged_prefill_gqa", "ragged_rope_append")
+                      "ragged_prefill_gqa", "ragged_prefill_gqa_fp8",
+                      "ragged_rope_append")

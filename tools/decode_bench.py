@@ -15,7 +15,11 @@ of the same shape as the yardstick.
 `ragged_prefill_gqa`, the same way over a decode-only step (64 rows at context
 8192), a chunk step (8 x 256 new tokens over a 4096-token prefix), both mixed,
 and the chunk step with window 4096 at prefix 32768 (new kernel only);
-8 kv heads, D 128, G 4, 8 and 7 (new kernel only)."""
+8 kv heads, D 128, G 4, 8 and 7 (new kernel only).
+
+`--prefill-kernels --fp8`: the same steps over pools made with `kv_quantize`:
+`ragged_prefill_fp8` (G 4 and 8, no window) and `ragged_prefill_gqa_fp8`, with
+`ragged_prefill_gqa` on the bf16 pool of the same shape as the yardstick."""
 import os
 import sys
 import time
@@ -95,9 +99,11 @@ def kernels(window, fp8=False, reps=30, rounds=5):
                 del kp, vp, arms
 
 
-def prefill_kernels(reps=20, rounds=3):
+def prefill_kernels(fp8=False, reps=20, rounds=3):
     """The fused-step kernels, `ragged_prefill` (G 4 and 8, no window) and
-    `ragged_prefill_gqa`, alternately over the same ragged steps."""
+    `ragged_prefill_gqa`, alternately over the same ragged steps; with `fp8`
+    `ragged_prefill_fp8` (G 4 and 8, no window), `ragged_prefill_gqa_fp8`
+    and `ragged_prefill_gqa` on the bf16 pool."""
     from deepspeed_amd.inference.ragged_batch import RaggedBatch
     from deepspeed_amd.ops.loader import get_ext
     ext = get_ext(required=True)
@@ -118,11 +124,29 @@ def prefill_kernels(reps=20, rounds=3):
             seqs.append((slot, t, ql, kv))
             t += ql
         b = RaggedBatch(seqs, n, smax, dev)
+        if fp8:
+            from deepspeed_amd.ops.functional import kv_quantize
+            (kc, ks), (vc, vs) = kv_quantize(kp), kv_quantize(vp)
         for G in ((4, 8) if window else (4, 8, 7)):
             q = torch.randn(t, G * Hk, D, device=dev, generator=g).bfloat16()
             arms = {"ragged_prefill_gqa": lambda: ext.ragged_prefill_gqa(
                 q, kp, vp, b.desc, b.max_qlen, b.max_kvlen, window)}
-            if not window and G != 7:
+            if fp8:
+                arms["ragged_prefill_gqa_fp8"] = \
+                    lambda: ext.ragged_prefill_gqa_fp8(
+                        q, kc, vc, ks, vs, b.desc, b.max_qlen, b.max_kvlen,
+                        window)
+                if not window and G != 7:
+                    arms["ragged_prefill_fp8"] = \
+                        lambda: ext.ragged_prefill_fp8(
+                            q, kc, vc, ks, vs, b.desc, b.max_qlen,
+                            b.max_kvlen)
+                new = arms["ragged_prefill_gqa_fp8"]().float()
+                for k, f in arms.items():
+                    if k != "ragged_prefill_gqa_fp8":
+                        d = (new - f().float()).abs().max().item()
+                        print(f"# G={G} {name} max |gqa_fp8 - {k}| = {d:.3e}")
+            elif not window and G != 7:
                 arms["ragged_prefill"] = lambda: ext.ragged_prefill(
                     q, kp, vp, b.desc, b.max_qlen, b.max_kvlen)
                 x, y = (f().float() for f in arms.values())
@@ -143,7 +167,7 @@ def prefill_kernels(reps=20, rounds=3):
 
 def main():
     if "--prefill-kernels" in sys.argv:
-        return prefill_kernels()
+        return prefill_kernels(fp8="--fp8" in sys.argv)
     if "--kernels" in sys.argv:
         w = sys.argv.index("--window") if "--window" in sys.argv else None
         return kernels(int(sys.argv[w + 1]) if w is not None else 0,
