@@ -23,6 +23,7 @@ class MixtralConfig(LlamaConfig):
     ep_size: int = 1
     capacity_factor: float = 1.25
     aux_loss_coef: float = 0.01
+    fused_moe_routing: bool = False     # HIP gate / dispatch / combine
 
 
 MIXTRAL_CONFIGS = {
@@ -50,7 +51,8 @@ class MixtralDecoderLayer(nn.Module):
         self.block_sparse_moe = MoE(cfg.hidden_size, expert,
                                     num_experts=cfg.num_experts,
                                     ep_size=cfg.ep_size, k=cfg.top_k,
-                                    capacity_factor=cfg.capacity_factor)
+                                    capacity_factor=cfg.capacity_factor,
+                                    fused_routing=cfg.fused_moe_routing)
 
     def forward(self, x, cos, sin, kv_cache=None):
         x = x + self.self_attn(self.input_layernorm(x), cos, sin,

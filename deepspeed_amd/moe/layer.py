@@ -12,7 +12,7 @@ class MoE(torch.nn.Module):
     def __init__(self, hidden_size, expert, num_experts=1, ep_size=1,
                  k=1, capacity_factor=1.0, eval_capacity_factor=1.0,
                  min_capacity=4, drop_tokens=True, use_residual=False,
-                 **kwargs):
+                 fused_routing=False, **kwargs):
         super().__init__()
         self.use_residual = use_residual
         assert num_experts % ep_size == 0, \
@@ -27,7 +27,8 @@ class MoE(torch.nn.Module):
         experts = Experts(expert, self.num_local_experts,
                           self.expert_group_name)
         self.deepspeed_moe = MOELayer(gate, experts, self.expert_group_name,
-                                      self.ep_size, self.num_local_experts)
+                                      self.ep_size, self.num_local_experts,
+                                      fused_routing=fused_routing)
         if use_residual:
             self.mlp = expert
             self.coefficient = torch.nn.Linear(hidden_size, 2)

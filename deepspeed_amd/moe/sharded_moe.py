@@ -87,9 +87,19 @@ def topkgating_indices(logits, k, capacity_factor, min_capacity=4,
     Returns (l_aux, topk_idx [S,k], weights [S,k] fp32, locations [S,k],
     keep [S,k] bool, capacity).
     """
+    capacity = _capacity(logits, capacity_factor * k, min_capacity)
+    return gating_indices_at_capacity(logits, k, capacity, drop_tokens,
+                                      ep_group)[:6]
+
+
+def gating_indices_at_capacity(logits, k, capacity, drop_tokens=True,
+                               ep_group=None):
+    """`topkgating_indices` at a given capacity. Returns its six results and
+    the 0/1 choice mask [S, E] (before dropping). The single definition of
+    the index-form gate: the HIP gate's torch fallback
+    (`ops.functional.moe_gate_topk`) is this function."""
     gates = F.softmax(logits, dim=1)
     num_tokens, num_experts = gates.shape
-    capacity = _capacity(gates, capacity_factor * k, min_capacity)
 
     topk_vals, topk_idx = torch.topk(gates, k, dim=1)  # [S, k]
     mask = torch.zeros_like(gates)
@@ -121,7 +131,7 @@ def topkgating_indices(logits, k, capacity_factor, min_capacity=4,
     vals = topk_vals * keep  # drop, then renormalize over kept experts
     denom = vals.sum(dim=1, keepdim=True).clamp(min=1e-9)
     weights = vals / denom
-    return l_aux, topk_idx, weights, loc_sj, keep, capacity
+    return l_aux, topk_idx, weights, loc_sj, keep, capacity, mask
 
 
 class TopKGate(torch.nn.Module):
@@ -154,8 +164,11 @@ class MOELayer(torch.nn.Module):
     """
 
     def __init__(self, gate, experts, ep_group_name, ep_size,
-                 num_local_experts):
+                 num_local_experts, fused_routing=False):
         super().__init__()
+        # route with ops.functional.moe_gate_topk / moe_dispatch /
+        # moe_combine (HIP on the GPU) instead of the torch index ops below
+        self.fused_routing = fused_routing
         self.gate = gate
         self.experts = experts
         self.ep_group = None
@@ -177,6 +190,8 @@ class MOELayer(torch.nn.Module):
                          torch.float32 else reshaped).float()
         cf = gate.capacity_factor if self.training \
             else gate.eval_capacity_factor
+        if self.fused_routing:
+            return self._forward_fused(input_, reshaped, logits, cf)
         self.l_aux, idx, w, loc, keep, C = topkgating_indices(
             logits, gate.k, cf, gate.min_capacity, gate.drop_tokens,
             ep_group=self.ep_group if self.ep_size > 1 else None)
@@ -213,4 +228,34 @@ class MOELayer(torch.nn.Module):
             .reshape(S, gate.k, d_model)
         wk = (w * keep).to(gathered.dtype).unsqueeze(-1)
         combined = (wk * gathered).sum(dim=1)
+        return combined.reshape(input_.shape)
+
+    def _forward_fused(self, input_, reshaped, logits, cf):
+        """The same layer on the routing functionals: the gate in three
+        launches, one pass over the rows each for dispatch and combine, and
+        no host sync when dropping."""
+        from ..ops import functional as Fops
+        gate = self.gate
+        d_model = reshaped.shape[-1]
+        E = logits.shape[1]
+        C = _capacity(logits, cf * gate.k, gate.min_capacity)
+        self.l_aux, idx, w, loc, keep, counts, slot_token = \
+            Fops.moe_gate_topk(
+                logits, gate.k, C, gate.drop_tokens,
+                ep_group=self.ep_group if self.ep_size > 1 else None)
+        C = slot_token.numel() // E     # grown to the longest queue, no-drop
+        self.exp_counts = keep.sum(0) if gate.k > 1 else None
+
+        dispatched = Fops.moe_dispatch(reshaped, idx, loc, keep, slot_token,
+                                       E, C)
+        if self.ep_size > 1:
+            dispatched = _AllToAll.apply(self.ep_group, dispatched)
+        dispatched = dispatched.reshape(self.ep_size, self.num_local_experts,
+                                        C, d_model)
+        expert_out = self.experts(dispatched)
+        expert_out = expert_out.reshape(E, C, d_model)
+        if self.ep_size > 1:
+            expert_out = _AllToAll.apply(self.ep_group, expert_out)
+        combined = Fops.moe_combine(expert_out, idx, loc, keep, w,
+                                    slot_token=slot_token)
         return combined.reshape(input_.shape)

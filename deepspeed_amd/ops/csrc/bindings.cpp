@@ -119,6 +119,24 @@ std::vector<at::Tensor> cross_entropy_fwd(at::Tensor logits,
 at::Tensor cross_entropy_bwd(at::Tensor logits, at::Tensor targets,
                              at::Tensor lse, at::Tensor dloss,
                              long ignore_index);
+long moe_gate_block_tokens(long E);
+std::vector<at::Tensor> moe_gate_rank(at::Tensor logits, long k);
+std::vector<at::Tensor> moe_gate_scan(at::Tensor block_counts,
+                                      at::Tensor block_gsum, long S, long k);
+std::vector<at::Tensor> moe_gate_finish(at::Tensor idx, at::Tensor vals,
+                                        at::Tensor rank, at::Tensor block_off,
+                                        at::Tensor counts, long C,
+                                        bool drop_tokens);
+at::Tensor moe_gate_topk_bwd(at::Tensor logits, at::Tensor idx,
+                             at::Tensor keep, at::Tensor counts,
+                             at::Tensor dweights, at::Tensor dl_aux);
+void moe_scatter_rows(at::Tensor out, at::Tensor x, at::Tensor slot_token,
+                      c10::optional<at::Tensor> scale, long k);
+void moe_gather_rows(at::Tensor out, at::Tensor src, at::Tensor idx,
+                     at::Tensor loc, at::Tensor keep,
+                     c10::optional<at::Tensor> w, long C);
+at::Tensor moe_gather_dot(at::Tensor dout, at::Tensor src, at::Tensor idx,
+                          at::Tensor loc, at::Tensor keep, long C);
 
 void bind_aio(py::module_& m);
 at::Tensor gemv_bf16(at::Tensor W, at::Tensor x);
@@ -259,4 +277,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("cross_entropy_fwd", &cross_entropy_fwd);
   m.def("cross_entropy_bwd", &cross_entropy_bwd);
+  m.def("moe_gate_block_tokens", &moe_gate_block_tokens, py::arg("E"));
+  m.def("moe_gate_rank", &moe_gate_rank, py::arg("logits"), py::arg("k"));
+  m.def("moe_gate_scan", &moe_gate_scan, py::arg("block_counts"),
+        py::arg("block_gsum"), py::arg("S"), py::arg("k"));
+  m.def("moe_gate_finish", &moe_gate_finish, py::arg("idx"), py::arg("vals"),
+        py::arg("rank"), py::arg("block_off"), py::arg("counts"),
+        py::arg("C"), py::arg("drop_tokens") = true);
+  m.def("moe_gate_topk_bwd", &moe_gate_topk_bwd, py::arg("logits"),
+        py::arg("idx"), py::arg("keep"), py::arg("counts"),
+        py::arg("dweights"), py::arg("dl_aux"));
+  m.def("moe_scatter_rows", &moe_scatter_rows, py::arg("out"), py::arg("x"),
+        py::arg("slot_token"), py::arg("scale") = c10::nullopt,
+        py::arg("k") = 1);
+  m.def("moe_gather_rows", &moe_gather_rows, py::arg("out"), py::arg("src"),
+        py::arg("idx"), py::arg("loc"), py::arg("keep"),
+        py::arg("w") = c10::nullopt, py::arg("C") = 1);
+  m.def("moe_gather_dot", &moe_gather_dot, py::arg("dout"), py::arg("src"),
+        py::arg("idx"), py::arg("loc"), py::arg("keep"), py::arg("C"));
 }

@@ -570,6 +570,267 @@ def ragged_prefill_attention_fp8(q, kpool, vpool, k_scale, v_scale, batch,
                                  batch, window=window)
 
 
+# ------------------------------------------------------------ MoE routing
+MOE_MAX_K = 8
+MOE_MAX_EXPERTS = 256
+
+
+def moe_gate_block_tokens(num_experts):
+    """Tokens per workgroup of the HIP gate kernels (`block_tokens` in
+    moe_routing.hip): the fp32 logits tile stays near 33 KB of LDS."""
+    E = num_experts
+    return 256 if E <= 32 else 128 if E <= 64 else 64 if E <= 128 else 32
+
+
+def _moe_slot_token(idx, loc, keep, num_experts, capacity):
+    """Inverse of the routing, without a host sync: slot e*C + c -> the flat
+    choice index s*k + j that owns it, -1 for an empty slot."""
+    n = num_experts * capacity
+    pos = torch.where(keep, idx.long() * capacity + loc.long(), n).reshape(-1)
+    st = torch.full((n + 1,), -1, dtype=torch.int32, device=idx.device)
+    st.scatter_(0, pos, torch.arange(pos.numel(), dtype=torch.int32,
+                                     device=idx.device))
+    return st[:n]
+
+
+def _moe_gate_topk_torch(logits, k, capacity, drop_tokens, ep_group):
+    from ..moe.sharded_moe import gating_indices_at_capacity
+    l_aux, idx, weights, loc, keep, capacity, mask = \
+        gating_indices_at_capacity(logits, k, capacity, drop_tokens, ep_group)
+    idx, loc = idx.to(torch.int32), loc.to(torch.int32)
+    return (l_aux, idx, weights, loc, keep, mask.sum(dim=0).to(torch.int32),
+            _moe_slot_token(idx, loc, keep, logits.shape[1], capacity))
+
+
+def _moe_nodrop_capacity(counts, capacity, ep_group):
+    """No-drop capacity: the longest queue, agreed on across the EP group so
+    the all-to-all shapes match. The one host sync of the no-drop mode."""
+    from .. import comm as dist
+    capacity = max(capacity, int(counts.max().item()))
+    if ep_group is not None and dist.get_world_size(ep_group) > 1:
+        t = torch.tensor([capacity], device=counts.device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=ep_group)
+        capacity = int(t.item())
+    return capacity
+
+
+class _MoEGateFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, k, capacity, drop_tokens, ep_group):
+        ext = get_ext(required=True)
+        logits = logits.contiguous()
+        idx, vals, rank, blocks, gsum = ext.moe_gate_rank(logits, k)
+        # `blocks` turns from per-block counts into per-block offsets
+        counts, l_aux = ext.moe_gate_scan(blocks, gsum, logits.shape[0], k)
+        if not drop_tokens:
+            capacity = _moe_nodrop_capacity(counts, capacity, ep_group)
+        loc, keep, weights, slot_token = ext.moe_gate_finish(
+            idx, vals, rank, blocks, counts, capacity, drop_tokens)
+        ctx.save_for_backward(logits, idx, keep, counts)
+        ctx.mark_non_differentiable(idx, loc, keep, counts, slot_token)
+        return l_aux, idx, weights, loc, keep, counts, slot_token
+
+    @staticmethod
+    def backward(ctx, dl_aux, _idx, dweights, *_):
+        logits, idx, keep, counts = ctx.saved_tensors
+        ext = get_ext(required=True)
+        if dl_aux is None:
+            dl_aux = logits.new_zeros(())
+        if dweights is None:
+            dweights = logits.new_zeros(idx.shape)
+        dlogits = ext.moe_gate_topk_bwd(
+            logits, idx, keep, counts, dweights.float().contiguous(),
+            dl_aux.float().contiguous())
+        return dlogits, None, None, None, None
+
+
+def moe_gate_topk(logits, k, capacity, drop_tokens=True, ep_group=None):
+    """Index-form top-k gate of fp32 logits [S, E] at capacity C.
+
+    Returns (l_aux, idx, weights, loc, keep, counts, slot_token):
+      idx [S,k] int32      the k experts of largest softmax gate; among equal
+                           gates the LOWER expert index wins on the HIP path
+                           (torch.topk, the fallback, promises no order);
+      loc [S,k] int32      tokens t < s that chose the same expert;
+      keep [S,k] bool      loc < C when dropping, all true otherwise;
+      weights [S,k] fp32   gates[idx] * keep / max(sum of kept, 1e-9);
+      counts [E] int32     tokens that chose each expert, before dropping;
+      l_aux                E*E/k * sum_e mean_s(gates) * mean_s(mask);
+      slot_token [E*C] int32   the choice s*k + j that owns slot e*C + loc,
+                           -1 for an empty slot.
+    With `drop_tokens=False` C grows to the longest queue (one host sync, and
+    a MAX all-reduce over `ep_group`); read it back as len(slot_token) // E.
+    Differentiable in `weights` and `l_aux`, the mask held constant.
+
+    fp32 on the GPU with 1 <= k <= 8 and k <= E <= 256 runs the HIP gate
+    (three launches, backward one); anything else
+    `moe.sharded_moe.gating_indices_at_capacity`, the definition both share.
+    S = 0 gives empty outputs and l_aux = 0.
+    """
+    S, E = logits.shape
+    hip = (logits.is_cuda and logits.dtype == torch.float32 and S > 0
+           and 1 <= k <= MOE_MAX_K and k <= E <= MOE_MAX_EXPERTS
+           and capacity >= 1 and S * MOE_MAX_K < 2 ** 31)
+    if not hip:
+        out = _moe_gate_topk_torch(logits, k, capacity, drop_tokens, ep_group)
+        if S == 0:      # a mean over no tokens is NaN
+            out = (logits.sum() * 0.0,) + out[1:]
+        return out
+    return _MoEGateFn.apply(logits, k, capacity, drop_tokens, ep_group)
+
+
+def _moe_rows_ok(*tensors):
+    """The row kernels' contract: bf16 / fp32 on the GPU, contiguous 2-d,
+    16-byte aligned, rows a whole number of 16-byte vectors."""
+    first = tensors[0]
+    return all(
+        t.is_cuda and t.dtype == first.dtype
+        and t.dtype in (torch.bfloat16, torch.float32) and t.dim() == 2
+        and t.is_contiguous() and t.shape[1] > 0
+        and (t.shape[1] * t.element_size()) % 16 == 0
+        and t.data_ptr() % 16 == 0 for t in tensors)
+
+
+def _moe_grad_rows(g):
+    g = g.contiguous()
+    return g if g.data_ptr() % 16 == 0 else g.clone()
+
+
+def _moe_routing_i32(idx, loc, keep):
+    return (idx.to(torch.int32).contiguous(), loc.to(torch.int32).contiguous(),
+            keep.contiguous())
+
+
+class _MoEDispatchFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, idx, loc, keep, slot_token, capacity, out):
+        ext = get_ext(required=True)
+        if out is None:
+            out = x.new_empty(slot_token.numel(), x.shape[1])
+        else:
+            ctx.mark_dirty(out)
+        ext.moe_scatter_rows(out.view(-1, x.shape[1]), x, slot_token, None,
+                             idx.shape[1])
+        ctx.save_for_backward(idx, loc, keep)
+        ctx.capacity = capacity
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, loc, keep = ctx.saved_tensors
+        ext = get_ext(required=True)
+        g = _moe_grad_rows(g.reshape(-1, g.shape[-1]))
+        dx = g.new_empty(idx.shape[0], g.shape[1])
+        ext.moe_gather_rows(dx, g, idx, loc, keep, None, ctx.capacity)
+        return dx, None, None, None, None, None, None
+
+
+def _moe_dispatch_torch(x, idx, loc, keep, num_experts, capacity):
+    S, k = idx.shape
+    n = num_experts * capacity
+    pos = torch.where(keep, idx.long() * capacity + loc.long(), n).reshape(-1)
+    tok = torch.arange(S, device=x.device).repeat_interleave(k)
+    # dropped choices land on row n, which is cut off
+    return x.new_zeros(n + 1, x.shape[1]).index_copy(
+        0, pos, x.index_select(0, tok))[:n]
+
+
+def moe_dispatch(x, idx, loc, keep, slot_token, num_experts, capacity,
+                 out=None):
+    """Rows of x [S, M] to their expert slots: returns [E, C, M] with
+    out[e, c] = x[s] for the kept choice (s, j) at idx = e, loc = c, and 0 in
+    every empty slot. `out` ([E, C, M] or [E*C, M]) supplies the storage;
+    every row of it is written.
+
+    bf16 / fp32 on the GPU, contiguous 16-byte-aligned rows that are a
+    multiple of 16 bytes wide: the `moe_scatter_rows` HIP kernel, one launch,
+    a bit-exact copy; backward is `moe_gather_rows`. Anything else runs torch
+    index ops (no host sync either).
+    """
+    M = x.shape[1]
+    n = num_experts * capacity
+    out2 = out.view(n, M) if out is not None else None
+    rows = (x,) if out2 is None else (x, out2)
+    if _moe_rows_ok(*rows) and idx.shape[1] <= MOE_MAX_K and n > 0:
+        idx, loc, keep = _moe_routing_i32(idx, loc, keep)
+        # `out` itself, not a view of it: autograd tracks the written tensor
+        res = _MoEDispatchFn.apply(x, idx, loc, keep, slot_token.contiguous(),
+                                   capacity, out)
+    else:
+        res = _moe_dispatch_torch(x, idx, loc, keep, num_experts, capacity)
+        if out2 is not None:
+            res = out2.copy_(res)
+    return res.view(num_experts, capacity, M)
+
+
+class _MoECombineFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, expert_out, idx, loc, keep, weights, slot_token,
+                capacity, out):
+        ext = get_ext(required=True)
+        if out is None:
+            out = expert_out.new_empty(idx.shape[0], expert_out.shape[1])
+        else:
+            ctx.mark_dirty(out)
+        ext.moe_gather_rows(out, expert_out, idx, loc, keep, weights,
+                            capacity)
+        ctx.save_for_backward(expert_out, idx, loc, keep, weights, slot_token)
+        ctx.capacity = capacity
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        expert_out, idx, loc, keep, weights, slot_token = ctx.saved_tensors
+        ext = get_ext(required=True)
+        g = _moe_grad_rows(g)
+        d_expert = dw = None
+        if ctx.needs_input_grad[0]:
+            d_expert = torch.empty_like(expert_out)
+            ext.moe_scatter_rows(d_expert, g, slot_token, weights,
+                                 idx.shape[1])
+        if ctx.needs_input_grad[4]:
+            dw = ext.moe_gather_dot(g, expert_out, idx, loc, keep,
+                                    ctx.capacity)
+        return d_expert, None, None, None, dw, None, None, None
+
+
+def _moe_combine_torch(expert_flat, idx, loc, keep, weights, capacity):
+    S, k = idx.shape
+    safe_pos = (idx.long() * capacity + loc.long()).reshape(-1) \
+        .clamp_(max=expert_flat.shape[0] - 1)
+    gathered = expert_flat.index_select(0, safe_pos) \
+        .reshape(S, k, expert_flat.shape[1])
+    wk = (weights * keep).to(gathered.dtype).unsqueeze(-1)
+    return (wk * gathered).sum(dim=1)
+
+
+def moe_combine(expert_out, idx, loc, keep, weights, out=None,
+                slot_token=None):
+    """Gate-weighted sum of each token's kept expert rows: expert_out
+    [E, C, M] -> [S, M], out[s] = sum_j weights[s, j] * expert_out[idx, loc]
+    over the kept choices. `out` [S, M] supplies the storage. `slot_token`
+    (from `moe_gate_topk`) spares backward rebuilding it.
+
+    Same requirements as `moe_dispatch`: the `moe_gather_rows` HIP kernel
+    (fp32 weights and accumulation, one rounding), backward
+    `moe_scatter_rows` scaled by the weights plus `moe_gather_dot` for the
+    weights' gradient. Anything else runs torch index ops, with the weights
+    rounded to the activation dtype first.
+    """
+    E, C, M = expert_out.shape
+    flat = expert_out.reshape(E * C, M)
+    rows = (flat,) if out is None else (flat, out)
+    if _moe_rows_ok(*rows) and idx.shape[1] <= MOE_MAX_K and idx.shape[0] > 0:
+        idx, loc, keep = _moe_routing_i32(idx, loc, keep)
+        if slot_token is None:
+            slot_token = _moe_slot_token(idx, loc, keep, E, C)
+        return _MoECombineFn.apply(flat, idx, loc, keep,
+                                   weights.float().contiguous(),
+                                   slot_token.contiguous(), C, out)
+    res = _moe_combine_torch(flat, idx, loc, keep, weights, C)
+    return res if out is None else out.copy_(res)
+
+
 def gds_handle(*a, **kw):
     """Parity stub for reference ops/aio GDS (GPUDirect Storage) builder.
 
