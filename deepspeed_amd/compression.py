@@ -10,6 +10,7 @@ import re
 import torch
 import torch.nn.functional as F
 
+from .ops.linear import WgradLinear
 from .utils.logging import log_dist
 
 
@@ -123,7 +124,7 @@ def init_compression(model, compression_config):
     n = 0
     for name, module in list(model.named_modules()):
         for child_name, child in list(module.named_children()):
-            if type(child) is torch.nn.Linear or \
+            if type(child) in (torch.nn.Linear, WgradLinear) or \
                     isinstance(child, LinearLayerCompress):
                 full = f"{name}.{child_name}" if name else child_name
                 # already-compressible modules take new techniques in

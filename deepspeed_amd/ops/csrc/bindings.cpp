@@ -139,6 +139,7 @@ at::Tensor moe_gather_dot(at::Tensor dout, at::Tensor src, at::Tensor idx,
                           at::Tensor loc, at::Tensor keep, long C);
 
 void bind_aio(py::module_& m);
+at::Tensor transpose_bf16(at::Tensor x);
 at::Tensor gemv_bf16(at::Tensor W, at::Tensor x);
 at::Tensor spatial_bias_add(at::Tensor a, at::Tensor bias,
                             c10::optional<at::Tensor> other);
@@ -208,6 +209,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("e5m2") = false);
   m.def("fp8_cast_transpose", &fp8_cast_transpose, py::arg("x"),
         py::arg("scale"), py::arg("e5m2") = false);
+  m.def("transpose_bf16", &transpose_bf16, py::arg("x"));
   m.def("gemv_bf16", &gemv_bf16);
   m.def("spatial_bias_add", &spatial_bias_add, py::arg("a"), py::arg("bias"),
         py::arg("other") = c10::nullopt);

@@ -144,9 +144,10 @@ class Fp8Linear(torch.nn.Linear):
     @classmethod
     def convert(cls, module, include=None):
         """Re-class matching nn.Linear instances in place (no copies)."""
+        from .linear import WgradLinear  # a plain Linear the engine re-classed
         n_conv = 0
         for name, child in module.named_modules():
-            if type(child) is torch.nn.Linear and \
+            if type(child) in (torch.nn.Linear, WgradLinear) and \
                     (include is None or any(tag in name for tag in include)):
                 child.__class__ = cls
                 n_conv += 1

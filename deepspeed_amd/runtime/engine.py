@@ -110,6 +110,12 @@ class DeepSpeedEngine(torch.nn.Module):
             apply_tensor_parallel_hf(model)
             add_tp_training_hooks(model)
 
+        # the plain nn.Linear layers that the user's own conversions
+        # (Fp8Linear, compression) and AutoTP left get their bf16 dW GEMM
+        # from transposed operands where that measured faster
+        from ..ops.linear import WgradLinear
+        WgradLinear.convert(model)
+
         self.dp_group = groups.get_sequence_data_parallel_group() \
             if sp > 1 else groups.get_data_parallel_group()
         self.dp_world_size = dist.get_world_size(self.dp_group)
